@@ -3,6 +3,17 @@
 (8,16,4096,64) bf16 (BASELINE.json metric, configs[2]), on 1, 2, 4 or 8 GPUs.
 
     python bench.py --gpus N --steps K --warmup W [--config c3|c4] [--split strong|weak]
+                    [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline figure needs: it builds the inputs, warms up, times
+exactly K steps and prints the result line. --full adds the side legs (N = 1): `extra`
+(causal, backward, fp32 config 2, the config-4 shard, the config-5 training step), the
+`cpu_baseline` and the `parity` of the timed output against the CPU reference; --no-extra
+and --no-cpu drop one of them from a --full run. --dump-outputs DIR writes what the last
+timed step computed (O, and with N = 1 the row statistics m and l) as DIR/<name>.npy,
+float32, at most 64 MB in all: whole arrays when they fit, else the same fixed seeded sample
+of (b,h,row) rows of each. The inputs are counter-seeded, so two runs with the same arguments
+see identical Q/K/V and two builds can be compared output for output.
 
 One "step" = one pass of the hot path (the bf16 MFMA forward kernel) over this rank's
 shard of the workload, with synthetic Q/K/V already resident in HBM. Since round 6 the timed
@@ -33,7 +44,7 @@ rank 0 prints ONE JSON line with the contract fields plus:
                  duration from HIP events on the launch stream) vs the dense bf16 MFMA
                  peak; "traffic" = HBM bytes per launch from the committed rocprofv3 PMC
                  capture (profiles/pmc_*.json), or null.
-  cpu_baseline : the C restatement of the reference's CPU fast_ops attention
+  cpu_baseline : (--full) the C restatement of the reference's CPU fast_ops attention
                  (oracle/attn_ref.c), timed on a bounded sample of heads of the same
                  workload on this host's cores (rank 0, N = 1 only).
 
@@ -433,6 +444,30 @@ def load_pmc_traffic(tag):
         return None, None, {}
 
 
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # all of --dump-outputs' files together stay under 64 MB
+
+
+def dump_outputs(torch, out_dir, o, m=None, l=None):
+    """--dump-outputs: the last timed step's O [.., N, d] (and m, l [.., N] when given) as
+    float32 out_dir/<name>.npy. When they do not fit the budget whole, every array keeps the
+    same sorted sample of its flattened (b,h,row) rows, drawn once from a fixed seed."""
+    import numpy as np
+    d = o.shape[-1]
+    rows = o.numel() // d
+    stats = [(n_, t) for n_, t in (("m", m), ("l", l)) if t is not None]
+    assert all(t.numel() == rows for _, t in stats)
+    keep = min(rows, DUMP_BUDGET_BYTES // (4 * (d + len(stats))))
+    idx = None
+    if keep < rows:
+        g = torch.Generator(device="cpu")
+        g.manual_seed(0)
+        idx = torch.randperm(rows, generator=g)[:keep].sort().values.to(o.device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in [("O", o.reshape(rows, d))] + [(n_, t.reshape(rows)) for n_, t in stats]:
+        a = t if idx is None else t.index_select(0, idx)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.float().cpu().numpy())
+
+
 def extra_legs(torch, _hip, time_fn):
     """Single-GPU side legs (rank 0, N = 1): causal forward, bf16 backward, config 2 fp32,
     and the config-4 per-GPU shard at 8 GPUs."""
@@ -658,8 +693,14 @@ def parse_args(argv=None):
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c3")
     ap.add_argument("--split", choices=("strong", "weak"), default="strong")
     ap.add_argument("--causal", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra (bwd, fp32) legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the side legs (N = 1): extra (causal, bwd, "
+                         "fp32, config 4 and 5), the CPU baseline and the parity check")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the extra (bwd, fp32) legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, at "
+                         "most 64 MB: a fixed seeded sample of rows when larger)")
     ap.add_argument("--policy", type=int, default=0, help="kernel policy (0 default)")
     ap.add_argument("--out", choices=("f32", "bf16"), default="f32",
                     help="the timed forward's O: f32 (default, MT_BF16_F32OUT: within north_star's "
@@ -705,7 +746,12 @@ def main():
     result, o_timed, qkv = run(args, attn_ml, torch, dist, world, rank, f"cuda:{local}", torch.bfloat16,
                                esize=2, out_esize=4 if args.out == "f32" else 2)
 
-    if rank == 0 and world == 1 and not args.no_extra and args.config == "c3":
+    if rank == 0 and args.dump_outputs:
+        # N > 1: the all-gathered O (m and l stay per rank)
+        m_l = ml[tuple(qkv[0].shape[:3])] if world == 1 else (None, None)
+        dump_outputs(torch, args.dump_outputs, o_timed, *m_l)
+
+    if rank == 0 and world == 1 and args.full and not args.no_extra and args.config == "c3":
         clock = Clock(torch, "cuda")
 
         def time_fn(fn, steps, warmup):
@@ -723,7 +769,7 @@ def main():
 
         result["extra"] = extra_legs(torch, _hip, time_fn)
 
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         cpu = cpu_baseline(CONFIGS[args.config])
         cpu["gpu_over_cpu"] = round(result["value"] / cpu["value"], 1) if cpu["value"] > 0 else None
         result["cpu_baseline"] = cpu

@@ -129,6 +129,43 @@ def test_gpus_must_match_world():
     assert r.returncode == 2 and "WORLD_SIZE" in r.stderr
 
 
+def test_plain_run_has_no_side_legs_by_default():
+    args = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 3
+    assert bench.parse_args(["--full"]).full is True
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files of O, m, l; whole when they fit the byte budget, else
+    the same seeded sorted sample of (b,h,row) rows of each, identical from call to call."""
+    g = torch.Generator().manual_seed(5)
+    o = torch.randn((2, 3, 16, 8), generator=g).bfloat16()
+    m, l = torch.randn((2, 3, 16), generator=g), torch.rand((2, 3, 16), generator=g)
+    bench.dump_outputs(torch, str(tmp_path / "whole"), o, m, l)
+    got = {n: np.load(tmp_path / "whole" / f"{n}.npy") for n in ("O", "m", "l")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    np.testing.assert_array_equal(got["O"], o.float().numpy().reshape(96, 8))
+    np.testing.assert_array_equal(got["m"], m.numpy().reshape(96))
+    np.testing.assert_array_equal(got["l"], l.numpy().reshape(96))
+    # a budget of 20 rows of (8 + 2) floats
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 20 * 10 * 4)
+    for d_ in ("s1", "s2"):
+        bench.dump_outputs(torch, str(tmp_path / d_), o, m, l)
+    s1, s2 = ({n: np.load(tmp_path / d_ / f"{n}.npy") for n in ("O", "m", "l")} for d_ in ("s1", "s2"))
+    assert s1["O"].shape == (20, 8) and s1["m"].shape == (20,) and s1["l"].shape == (20,)
+    assert sum(a.nbytes for a in s1.values()) <= 20 * 10 * 4
+    for n in s1:
+        np.testing.assert_array_equal(s1[n], s2[n])
+    # the sample is rows of the whole arrays, in order, the same rows in every array
+    rows = [int(np.flatnonzero(got["m"] == x)[0]) for x in s1["m"]]
+    assert rows == sorted(set(rows))
+    np.testing.assert_array_equal(s1["O"], got["O"][rows])
+    np.testing.assert_array_equal(s1["l"], got["l"][rows])
+    # O alone (the all-gathered output of an N > 1 run)
+    bench.dump_outputs(torch, str(tmp_path / "o"), o)
+    assert sorted(p.name for p in (tmp_path / "o").iterdir()) == ["O.npy"]
+
+
 def test_occupancy_chunks_rule():
     """The end-to-end leg's default chunk count (minitorch/shard.py occupancy_chunks) for
     BASELINE configs 3 and 4 at 1, 2, 4 and 8 ranks: a chunk keeps at least one workgroup per
