@@ -70,7 +70,9 @@ int mt_flash_attn_fwd(int dtype, int causal, const void* q, const void* k, const
  * the reference's [B, to_len] additive padding mask does in the fused softmax
  * (src/softmax_kernel.cu:26-33). Queries are not masked (a padded query attends the valid
  * keys). A row with kv_len = 0 gets O = 0, m = -inf, l = 0. bf16 runs the generic / ring
- * kernels here (the d = 64 / 128 MFMA schedules have no per-row key bound). */
+ * kernels here (the d = 64 / 128 MFMA schedules have no per-row key bound), and so does
+ * MT_BF16_F32OUT: with kv_len its fp32 O is those kernels' result before the bf16 rounding
+ * (fa_fwd_generic_ring for d <= 64, fa_fwd_generic above), the same (m, l) either way. */
 int mt_flash_attn_fwd_varlen(int dtype, int causal, const void* q, const void* k, const void* v,
                              void* o, float* m, float* l, int64_t B, int64_t H, int64_t N,
                              int64_t d, const int64_t* q_strides, const int64_t* k_strides,

@@ -59,10 +59,11 @@ def grad_bounds(q, k, v, do, causal, atol=1e-3, r=R_BF16, kv=None, r_dq=None):
             atol + r * (P.T @ do))                                 # dV
 
 
-def grad_bounds_torch(q, k, v, do, causal, atol=1e-3, r=R_BF16, r_dq=None):
+def grad_bounds_torch(q, k, v, do, causal, atol=1e-3, r=R_BF16, r_dq=None, kv=None):
     """grad_bounds for a batch of heads [n, N, d] as fp64 torch tensors on the device (the
     same arithmetic; used where the NumPy form over every head of a full-size config would
-    take minutes of host time). Returns the dQ, dK, dV bounds [n, N, d] as fp64 tensors."""
+    take minutes of host time). kv: valid keys per head [n] (key padding, as head_terms).
+    Returns the dQ, dK, dV bounds [n, N, d] as fp64 tensors."""
     import torch
     q, k, v, do = (t.to(torch.float64) for t in (q, k, v, do))
     n, N, d = q.shape
@@ -70,9 +71,14 @@ def grad_bounds_torch(q, k, v, do, causal, atol=1e-3, r=R_BF16, r_dq=None):
     S = torch.matmul(q, k.transpose(1, 2)) * sc
     if causal:
         S.masked_fill_(torch.ones(N, N, dtype=torch.bool, device=q.device).triu(1), float("-inf"))
-    S -= S.amax(dim=2, keepdim=True)
+    if kv is not None:
+        kv = torch.as_tensor(kv, device=q.device).reshape(n, 1, 1)
+        S.masked_fill_(torch.arange(N, device=q.device).reshape(1, 1, N) >= kv, float("-inf"))
+    mx = S.amax(dim=2, keepdim=True)
+    S -= torch.where(torch.isneginf(mx), torch.zeros_like(mx), mx)
     P = torch.exp(S)
-    P /= P.sum(dim=2, keepdim=True)
+    tot = P.sum(dim=2, keepdim=True)
+    P = torch.where(tot > 0, P / torch.where(tot > 0, tot, torch.ones_like(tot)), torch.zeros_like(P))
     del S
     O = torch.matmul(P, v)
     delta = (do * O).sum(dim=2, keepdim=True)

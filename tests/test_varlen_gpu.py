@@ -3,11 +3,16 @@
 The contract is the reference's padding mask (src/softmax_kernel.cu:26-33: attn_mask[B,
 to_len], -inf for padding tokens), pinned by the reference-generated fixtures
 tests/golden/attn_varlen*.npz (oracle/gen_golden.py; checked in test_flash_gpu.py's golden
-test and tests/test_oracle.py). Here: random shapes through every kernel family that takes
-kv_len (the fp32 / small-d ring kernels, the generic kernels at d = 128, bf16 d = 64's ring
-forward and fused backward), ragged N, a row with no valid key (O = 0, zero gradients) and
-a full row, causal or not; then the minitorch MultiHeadAttention on a padded batch, whose
-flash, fused-softmax and plain branches must agree.
+test and tests/test_oracle.py). Here: random N(0,1) shapes through some of the kernel families
+that take kv_len (the fp32 / small-d ring kernels, fp32 d = 128's ring forward and generic
+backward, bf16 d = 64's ring forward and fused backward, unpaired and causal paired), ragged N,
+a row with no valid key (O = 0, zero gradients) and a full row, causal or not; then the
+minitorch MultiHeadAttention on a padded batch, whose flash, fused-softmax and plain branches
+must agree. These inputs and kv_len values cannot show a mask that is off by one key: that, and
+every other family (bf16 d = 128 / 96 / 48 / 32 / 20, fp32 d = 200 / 20 / 18, fp32 O, policies
+1 and 121, misaligned and permuted rows, the paired and chip-filling grids, the legacy backward
+entry, the fused backward's head groups, the [0, N] clamp), is tests/test_varlen_matrix_gpu.py
+on the boundary-sensitive inputs of tests/varlen_cases.py.
 
 Tolerances: fp32 1e-5 max-abs (the reference MHA bound); bf16 against the oracle on the same
 bf16-rounded inputs under the elementwise bounds of tests/bounds.py.
