@@ -59,7 +59,10 @@ int mt_scratch_release(void);
 /* ---- FlashAttention, device pointers ------------------------------------- */
 /* O = softmax(Q Kᵀ/√d [causal]) V;  m[b,h,n] = row max of the scaled logits,
  * l[b,h,n] = Σ exp(s − m)  (P = exp(s − m)/l, the reference contract,
- * src/flashattention_kernel.cu:194). m, l are fp32 [B*H*N] and may be NULL. */
+ * src/flashattention_kernel.cu:194). m, l are fp32 [B*H*N] and may be NULL.
+ * The fp32 entry points (MT_F32, forward and backward, and the host-pointer launchers below)
+ * require finite Q, K, V, O and dO: they form fp32 products from three bf16 pieces per value,
+ * which are NaN for a ±inf value, and may return NaN where an IEEE fp32 product gives ±inf. */
 int mt_flash_attn_fwd(int dtype, int causal, const void* q, const void* k, const void* v,
                       void* o, float* m, float* l, int64_t B, int64_t H, int64_t N, int64_t d,
                       const int64_t* q_strides, const int64_t* k_strides,
@@ -165,7 +168,12 @@ int mt_tensor_zip(int fn, float* out, const int64_t* out_shape, const int64_t* o
                   int out_dims, const float* a, const int64_t* a_shape, const int64_t* a_strides,
                   int a_dims, const float* b, const int64_t* b_shape, const int64_t* b_strides,
                   int b_dims, void* stream);
-/* out has a's shape with shape[reduce_dim] = 1; out = fn(start, fn-fold of the axis). */
+/* out has a's shape with shape[reduce_dim] = 1; out = fn(start, fn-fold of the axis): `start`
+ * enters exactly once per output element, whatever kernel the shape selects. The fold's
+ * association is fixed for a given shape and layout (a repeated call is bitwise equal) but
+ * differs between shapes. ±inf follow IEEE in add and mul folds and compare as usual in a max
+ * fold. The result of a max reduction (fn 16, `x > y ? x : y`) over an axis that holds a NaN is
+ * unspecified: that select is not associative under NaN, so the value depends on the fold order. */
 int mt_tensor_reduce(int fn, float* out, const int64_t* out_shape, const int64_t* out_strides,
                      const float* a, const int64_t* a_shape, const int64_t* a_strides, int dims,
                      int reduce_dim, float start, void* stream);
@@ -179,7 +187,9 @@ int mt_matmul_f32(float* c, const float* a, const float* b, int64_t batch, int64
 /* 0 (default): rocBLAS for plain layouts; 1: the library's own fp32-MFMA GEMM kernel only;
  * 2: the library's own fp32-accurate GEMM on the bf16 MFMA (three bf16 pieces per operand:
  * 128x128 tiles where they fill the chip, else 64x64 with split-K); 3: that GEMM on 64x64
- * tiles only (A/B). The environment variable MT_GEMM_BACKEND sets the initial value. */
+ * tiles only (A/B). The environment variable MT_GEMM_BACKEND sets the initial value.
+ * Every backend propagates ±inf and NaN operands as an IEEE fp32 product does (backends 2 and
+ * 3 stage a non-finite value as its own piece; inf times a finite |b| < 2^-126 is NaN there). */
 void mt_set_gemm_backend(int backend);
 
 /* out[0..n) <- U[0,1) from a stateless counter-based hash of (seed, index). Replaces the

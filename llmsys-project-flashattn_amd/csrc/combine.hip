@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include <rocblas/rocblas.h>
@@ -713,24 +714,28 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(GemmX3Args g) {
                  : chunk(B, g.sbk, g.N, n0 + 4 * (c % 16), k0 + c / 16, false);
     }
   };
-  auto store = [&](int st) __attribute__((always_inline)) {
+  // ±inf / NaN operands stay IEEE (fa_common.h x3_split2_nf): one check of the stage's 16 values
+  // per thread, then the plain split or, for the rare thread that holds one, the guarded split
+  auto store_as = [&](int st, auto nfc) __attribute__((always_inline)) {
+    constexpr bool NF = decltype(nfc)::value;
     bf16* base = sm + st * kGxStage;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int c = tid + 256 * i;
 #pragma unroll
       for (int op = 0; op < 2; ++op) {
-        const float4 v = op ? rb[i] : ra[i];
         const bool kc = op ? BK : AK;
-        unsigned h0, m0_, l0, h1, m1, l1;
-        x3_split2(v.x, v.y, h0, m0_, l0);
-        x3_split2(v.z, v.w, h1, m1, l1);
-        bf16* pl = base + 3 * op * kGxPlane + (kc ? (c / 8) * kGxLDK + 4 * (c % 8) : (c / 16) * kGxLDR + 4 * (c % 16));
-        *(uint2*)(pl) = make_uint2(h0, h1);
-        *(uint2*)(pl + kGxPlane) = make_uint2(m0_, m1);
-        *(uint2*)(pl + 2 * kGxPlane) = make_uint2(l0, l1);
+        x3_store4_sel<NF>(base + 3 * op * kGxPlane +
+                              (kc ? (c / 8) * kGxLDK + 4 * (c % 8) : (c / 16) * kGxLDR + 4 * (c % 16)),
+                          kGxPlane, op ? rb[i] : ra[i]);
       }
     }
+  };
+  auto store = [&](int st) __attribute__((always_inline)) {
+    if (x3_any_nonfinite(ra[0]) | x3_any_nonfinite(ra[1]) | x3_any_nonfinite(rb[0]) | x3_any_nonfinite(rb[1]))
+      store_as(st, std::true_type{});
+    else
+      store_as(st, std::false_type{});
   };
   // the fragment of k step ks for row `row` (m or n) of a plane: row reads or transposed reads
   typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
@@ -837,16 +842,23 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_big(GemmX3Args g) {
                  : chunk(B, g.sbk, g.N, n0 + 4 * (c % 32), k0 + c / 32, false);
     }
   };
-  auto store = [&](int st) __attribute__((always_inline)) {
+  auto store_as = [&](int st, auto nfc) __attribute__((always_inline)) {  // as gemm_x3_kernel's
+    constexpr bool NF = decltype(nfc)::value;
     bf16* base = smb + st * kGbStage;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int c = tid + 256 * i;
-      x3_store4(base + (AK ? (c / 4) * kGbLDK + 4 * (c % 4) : (c / 32) * kGbLDR + 4 * (c % 32)), kGbPlane,
-                __builtin_bit_cast(uint4, ra[i]));
-      x3_store4(base + 3 * kGbPlane + (BK ? (c / 4) * kGbLDK + 4 * (c % 4) : (c / 32) * kGbLDR + 4 * (c % 32)),
-                kGbPlane, __builtin_bit_cast(uint4, rb[i]));
+      x3_store4_sel<NF>(base + (AK ? (c / 4) * kGbLDK + 4 * (c % 4) : (c / 32) * kGbLDR + 4 * (c % 32)), kGbPlane,
+                        ra[i]);
+      x3_store4_sel<NF>(base + 3 * kGbPlane + (BK ? (c / 4) * kGbLDK + 4 * (c % 4) : (c / 32) * kGbLDR + 4 * (c % 32)),
+                        kGbPlane, rb[i]);
     }
+  };
+  auto store = [&](int st) __attribute__((always_inline)) {
+    if (x3_any_nonfinite(ra[0]) | x3_any_nonfinite(ra[1]) | x3_any_nonfinite(rb[0]) | x3_any_nonfinite(rb[1]))
+      store_as(st, std::true_type{});
+    else
+      store_as(st, std::false_type{});
   };
   typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
   auto frag = [&](const bf16* pl, int row, int ks, bool kc) -> bf16x8 {

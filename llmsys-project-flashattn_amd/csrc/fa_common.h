@@ -100,7 +100,8 @@ template <typename T> __device__ __forceinline__ Frag<T> acc_frag(const f32x16& 
 }
 
 // ---- fp32 products on the bf16 MFMA ("x3": three bf16 pieces per fp32 value) --------------
-// x = x1 + x2 + x3 exactly for normal fp32 x: x1 = x truncated to its top 16 bits (a bf16),
+// x = x1 + x2 + x3 exactly for finite normal fp32 x (not for ±inf or NaN: inf − inf makes the
+// middle and low pieces NaN; see x3_split2_nf): x1 = x truncated to its top 16 bits (a bf16),
 // r1 = x − x1 (exact, ≤ 16 significant bits), x2 = r1 truncated, r2 = r1 − x2 (exact, ≤ 8
 // significant bits, so x3 = r2's top 16 bits is r2). A product a·b then takes the six bf16
 // MFMA terms a1b1 + a1b2 + a2b1 + a1b3 + a3b1 + a2b2 (each bf16·bf16 product is exact in
@@ -151,6 +152,50 @@ __device__ __forceinline__ void x3_store4(bf16* dst, int plane, const uint4& v) 
   unsigned h0, m0, l0, h1, m1, l1;
   x3_split2(f.x, f.y, h0, m0, l0);
   x3_split2(f.z, f.w, h1, m1, l1);
+  *(uint2*)(dst) = make_uint2(h0, h1);
+  *(uint2*)(dst + plane) = make_uint2(m0, m1);
+  *(uint2*)(dst + 2 * plane) = make_uint2(l0, l1);
+}
+// The split with ±inf and NaN operands kept IEEE (the GEMM staging of combine.hip only: once per
+// element per tile; the flash kernels' in-loop splits stay x3_split2 and require finite inputs).
+// Zeroing m and l and keeping h = ±inf is not enough: the six-term product pairs a's h piece with
+// b's m and l pieces, which are exactly zero for every b that is a bf16 value (1.0, a one-hot
+// entry), and inf·0 = NaN. Only the l piece meets nothing but the other operand's h piece
+// (mma_x3: mm, lh, hl, mh, hm, hh), so a non-finite x goes in as (h, m, l) = (±1, 0, x): against a
+// finite b the terms are x·b.h + (±b) = ±inf (NaN for b = 0, as IEEE), against another
+// non-finite y they are x·(±1) + (±1)·y ± 1: inf·inf = inf, inf·(−inf) = −inf, NaN stays NaN.
+// (b.h is zero only for |b| below the bf16 range, 2^-126 with the MFMA's denormal flush: there
+// inf·b is NaN instead of ±inf.) A NaN's top half gets the quiet bit so that truncation cannot
+// turn it into inf.
+__device__ __forceinline__ void x3_split2_nf(float x, float y, unsigned& h, unsigned& m, unsigned& l) {
+  x3_split2(x, y, h, m, l);
+  const unsigned ux = __float_as_uint(x), uy = __float_as_uint(y);
+  if ((ux & 0x7f800000u) == 0x7f800000u) {
+    h = (h & 0xffff0000u) | ((ux >> 16) & 0x8000u) | 0x3f80u;
+    m &= 0xffff0000u;
+    l = (l & 0xffff0000u) | (ux >> 16) | ((ux & 0x007fffffu) ? 0x0040u : 0u);
+  }
+  if ((uy & 0x7f800000u) == 0x7f800000u) {
+    h = (h & 0x0000ffffu) | (uy & 0x80000000u) | 0x3f800000u;
+    m &= 0x0000ffffu;
+    l = (l & 0x0000ffffu) | (uy & 0xffff0000u) | ((uy & 0x007fffffu) ? 0x00400000u : 0u);
+  }
+}
+// NF: the guarded split (a thread takes it only for a stage in which x3_any_nonfinite saw one)
+template <bool NF>
+__device__ __forceinline__ void x3_split2_sel(float x, float y, unsigned& h, unsigned& m, unsigned& l) {
+  if constexpr (NF) x3_split2_nf(x, y, h, m, l);
+  else x3_split2(x, y, h, m, l);
+}
+__device__ __forceinline__ int x3_any_nonfinite(const float4& f) {  // one v_cmp_class_f32 per value
+  return (int)!__builtin_isfinite(f.x) | (int)!__builtin_isfinite(f.y) | (int)!__builtin_isfinite(f.z) |
+         (int)!__builtin_isfinite(f.w);
+}
+template <bool NF>
+__device__ __forceinline__ void x3_store4_sel(bf16* dst, int plane, const float4& f) {
+  unsigned h0, m0, l0, h1, m1, l1;
+  x3_split2_sel<NF>(f.x, f.y, h0, m0, l0);
+  x3_split2_sel<NF>(f.z, f.w, h1, m1, l1);
   *(uint2*)(dst) = make_uint2(h0, h1);
   *(uint2*)(dst + plane) = make_uint2(m0, m1);
   *(uint2*)(dst + 2 * plane) = make_uint2(l0, l1);
