@@ -109,6 +109,46 @@ int mt_flash_attn_bwd_v3(int dtype, int causal, const void* q, const void* k, co
                          int64_t d, const int64_t* strides, const int* kv_len,
                          void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- KV-cache decode attention, device pointers ---------------------------- */
+/* Generation: Nq (1..8) new query rows per (batch, head) against a cache of Nk key / value
+ * rows, of which the first n = clamp(kv_len[b], 0, Nk) are visible (kv_len: device int32 [B];
+ * NULL = Nk). The queries are the LAST Nq positions of the row: with causal != 0 query i sees
+ * the keys j < n - Nq + 1 + i (the causal mask aligned bottom-right), else every key j < n.
+ * A query with no visible key gets O = 0, m = -inf, l = 0. Rows j >= n are never read: the
+ * cache tail may be uninitialised memory.
+ *   q, o:              [B, H, Nq, d], strides (batch, head, row) in elements, NULL = contiguous
+ *   k_cache, v_cache:  [B, H, Nk, d] likewise (e.g. [B, Nk, H, d] storage seen through strides)
+ *   m, l:              fp32 [B*H*Nq] or NULL; m + log(l) is the row's log-sum-exp
+ * dtype: MT_F32, MT_BF16, or MT_BF16_F32OUT (bf16 Q/K/V, fp32 O). Requires 1 <= Nq <= 8,
+ * d <= 256 and 16-B rows: d, every stride and every base pointer a multiple of 16 bytes;
+ * anything else returns a status before any device call.
+ * The keys are split over mt_flash_attn_decode_splits workgroups per (b, h), each writing its
+ * fp32 (m, l, unnormalised O) to the workspace ([B*H*Nq*splits][d] O, then [B*H*Nq*splits][2]
+ * (m in log2 units, l); nothing with one split), merged in split order by a second launch on
+ * the same stream: bit-reproducible. The split count is a function of the arguments of
+ * mt_flash_attn_decode_splits only, never of kv_len, so a captured launch can be replayed as
+ * the cache fills. A workspace below mt_flash_attn_decode_workspace_bytes is an error and
+ * launches nothing. */
+int mt_flash_attn_decode_splits(int dtype, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t d,
+                                int64_t* span_keys, int64_t* tile_keys);
+/* returns the split count (>= 1), or <= 0 on bad sizes; span_keys: keys per split;
+ * tile_keys: keys one wave takes per inner step (either may be NULL) */
+int64_t mt_flash_attn_decode_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t Nq, int64_t Nk,
+                                             int64_t d);
+int mt_flash_attn_decode(int dtype, int causal, const void* q, const void* k_cache, const void* v_cache,
+                         void* o, float* m, float* l, int64_t B, int64_t H, int64_t Nq, int64_t Nk,
+                         int64_t d, const int64_t* q_strides, const int64_t* k_strides,
+                         const int64_t* v_strides, const int64_t* o_strides, const int* kv_len,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+/* Copies the Nq new K and V rows of every (b, h) ([B, H, Nq, d]) into the caches
+ * ([B, H, Nmax, d]) at rows pos[b] .. pos[b] + Nq - 1 (pos: device int32 [B]); rows outside
+ * [0, Nmax) are dropped and nothing else in the caches is written. 16-B rows as above. */
+int mt_kv_cache_append(int dtype, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                       int64_t B, int64_t H, int64_t Nq, int64_t Nmax, int64_t d,
+                       const int64_t* knew_strides, const int64_t* vnew_strides,
+                       const int64_t* kcache_strides, const int64_t* vcache_strides,
+                       const int* pos, void* stream);
+
 /* ---- FlashAttention, reference-compatible host pointers (fp32) ------------ */
 /* reference src/flashattention_kernel.cu:259 */
 void launch_flashattention_forward(float* Q, float* K, float* V, float* O, float* l, float* m,

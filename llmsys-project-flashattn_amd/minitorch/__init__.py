@@ -17,6 +17,7 @@ from .tensor_functions import *  # noqa: F401,F403
 from .tensor_ops import *  # noqa: F401,F403
 from .modules_basic import *  # noqa: F401,F403
 from .modules_transfomer import *  # noqa: F401,F403
+from .kv_cache import *  # noqa: F401,F403
 
 
 def __getattr__(name):

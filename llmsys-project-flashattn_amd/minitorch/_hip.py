@@ -52,6 +52,12 @@ _PROTOS = {
                                         _i64, _i64, _i64, _i64, _i64p, _vp, _vp, _vp]),
     "mt_flash_attn_bwd_v3": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _i64, _i64, _i64, _i64, _i64p, _vp, _vp, _i64, _vp]),
+    "mt_flash_attn_decode_splits": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _i64p, _i64p]),
+    "mt_flash_attn_decode_workspace_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64]),
+    "mt_flash_attn_decode": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                    _i64p, _i64p, _i64p, _i64p, _vp, _vp, _i64, _vp]),
+    "mt_kv_cache_append": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                  _i64p, _i64p, _i64p, _i64p, _vp, _vp]),
     "mt_attn_softmax_fw": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64p, _int, _vp]),
     "mt_attn_softmax_bw": (_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "mt_layernorm_fw": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
@@ -307,6 +313,88 @@ def flash_bwd(q, k, v, o, do, m, l, causal: bool = False, dq=None, dk=None, dv=N
                                      workspace.data_ptr(), workspace.numel() * workspace.element_size(),
                                      st), "mt_flash_attn_bwd_v3")
     return dq, dk, dv
+
+
+def _decode_code(q, out, out_dtype) -> int:
+    torch = _torch()
+    code = dtype_code(q)
+    if q.dtype == torch.bfloat16 and (out_dtype == torch.float32 or
+                                      (out is not None and out.dtype == torch.float32)):
+        code = 2  # MT_BF16_F32OUT
+    return code
+
+
+def decode_splits(dtype: int, B: int, H: int, Nq: int, Nk: int, d: int):
+    """(splits, span_keys, tile_keys) of mt_flash_attn_decode at these sizes (dtype: an MT_*
+    code): how many workgroups share the keys of one (batch, head), the keys each takes and the
+    keys one wave takes per inner step. A function of the sizes only."""
+    span, tile = ctypes.c_int64(0), ctypes.c_int64(0)
+    n = lib().mt_flash_attn_decode_splits(dtype, B, H, Nq, Nk, d, ctypes.byref(span), ctypes.byref(tile))
+    if n <= 0:
+        raise ValueError(lib().mt_last_error().decode(errors="replace"))
+    return n, span.value, tile.value
+
+
+def decode_workspace_bytes(dtype: int, B: int, H: int, Nq: int, Nk: int, d: int) -> int:
+    n = lib().mt_flash_attn_decode_workspace_bytes(dtype, B, H, Nq, Nk, d)
+    if n < 0:
+        raise ValueError(lib().mt_last_error().decode(errors="replace"))
+    return int(n)
+
+
+def flash_decode(q, k_cache, v_cache, kv_len=None, causal: bool = True, out=None, m=None, l=None,
+                 workspace=None, out_dtype=None, stream: Optional[int] = None):
+    """Decode attention (mt_flash_attn_decode): q [B,H,Nq,d] (Nq <= 8, the last Nq positions of
+    each row) against the caches [B,H,Nk,d] (any strides with unit-stride d), of which the first
+    kv_len[b] rows are visible (None: all Nk). Returns (O, m, l); m, l fp32 [B,H,Nq]. workspace:
+    a device buffer of at least decode_workspace_bytes (allocated when None)."""
+    torch = _torch()
+    _check_dev(q, k_cache, v_cache)
+    B, H, Nq, d = q.shape
+    Nk = k_cache.shape[2]
+    if k_cache.shape != (B, H, Nk, d) or v_cache.shape != k_cache.shape:
+        raise ValueError(f"cache shapes {tuple(k_cache.shape)} {tuple(v_cache.shape)} do not match q {tuple(q.shape)}")
+    if not (q.dtype == k_cache.dtype == v_cache.dtype):
+        raise TypeError("q/k_cache/v_cache dtypes differ")
+    code = _decode_code(q, out, out_dtype)
+    if out is None:
+        out = torch.empty((B, H, Nq, d), dtype=torch.float32 if code == 2 else q.dtype, device=q.device)
+    if m is None:
+        m = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    if l is None:
+        l = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    need = lib().mt_flash_attn_decode_workspace_bytes(code, B, H, Nq, Nk, d)
+    if workspace is None and need > 0:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=q.device)
+    kv = _kv_arg(kv_len, B, q.device)
+    st = stream_ptr(q.device) if stream is None else stream
+    check(lib().mt_flash_attn_decode(
+        code, int(causal), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(),
+        m.data_ptr(), l.data_ptr(), B, H, Nq, Nk, d, strides3(q), strides3(k_cache), strides3(v_cache),
+        strides3(out), None if kv is None else kv.data_ptr(),
+        None if workspace is None else workspace.data_ptr(),
+        0 if workspace is None else workspace.numel() * workspace.element_size(), st),
+        "mt_flash_attn_decode")
+    return out, m, l
+
+
+def kv_cache_append(k_new, v_new, k_cache, v_cache, pos, stream: Optional[int] = None) -> None:
+    """Copy the new rows k_new / v_new [B,H,Nq,d] into the caches [B,H,Nmax,d] at rows
+    pos[b] .. pos[b] + Nq - 1 (pos: [B] int32 on the device; rows past the capacity are dropped)."""
+    torch = _torch()
+    _check_dev(k_new, v_new, k_cache, v_cache)
+    B, H, Nq, d = k_new.shape
+    Nmax = k_cache.shape[2]
+    if v_new.shape != k_new.shape or k_cache.shape != (B, H, Nmax, d) or v_cache.shape != k_cache.shape:
+        raise ValueError("kv_cache_append: shapes do not match")
+    if not (k_new.dtype == v_new.dtype == k_cache.dtype == v_cache.dtype):
+        raise TypeError("kv_cache_append: dtypes differ")
+    p = _kv_arg(pos, B, k_new.device)
+    st = stream_ptr(k_new.device) if stream is None else stream
+    check(lib().mt_kv_cache_append(
+        dtype_code(k_new), k_new.data_ptr(), v_new.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+        B, H, Nq, Nmax, d, strides3(k_new), strides3(v_new), strides3(k_cache), strides3(v_cache),
+        p.data_ptr(), st), "mt_kv_cache_append")
 
 
 def scratch_bytes() -> int:

@@ -492,3 +492,34 @@ class HipKernelOps(TensorOps):
     @staticmethod
     def flash_attention_causal_bw(Q, K, V, O, dO, m, l, kv_len=None):
         return HipKernelOps._flash_bw(Q, K, V, O, dO, m, l, True, kv_len)
+
+    # ---- generation: KV-cache decode attention (mt_flash_attn_decode / mt_kv_cache_append) ----
+    @staticmethod
+    def _i32(t):
+        """A [B] count vector as the device int32 tensor the C ABI takes: a torch int32 tensor
+        as it is (a KVCache's length), a minitorch Tensor converted."""
+        import torch
+        if isinstance(t, Tensor):
+            return _torch_view(t).reshape(-1).to(torch.int32)
+        return t
+
+    @staticmethod
+    def flash_attention_decode(Q: Tensor, Kc: Tensor, Vc: Tensor, kv_len=None, causal: bool = True) -> Tensor:
+        """O [B,H,Nq,d] of the Nq <= 8 newest query rows against the caches Kc / Vc
+        [B,H,Nmax,d], of which the first kv_len[b] rows are visible (the queries are the last Nq
+        of them). Inference only. O is laid out like Q's storage (as _flash_fw does)."""
+        import torch
+        B, H, Nq, d = Q.shape
+        so = _layout_like(Q)
+        o = torch.empty(B * H * Nq * d, dtype=torch.float32, device="cuda")
+        _hip.flash_decode(_torch_view(Q), _torch_view(Kc), _torch_view(Vc),
+                          kv_len=None if kv_len is None else HipKernelOps._i32(kv_len), causal=causal,
+                          out=torch.as_strided(o, (B, H, Nq, d), so))
+        return _wrap(o, (B, H, Nq, d), Q.backend, so)
+
+    @staticmethod
+    def kv_cache_append(Knew: Tensor, Vnew: Tensor, Kc: Tensor, Vc: Tensor, pos) -> None:
+        """Write the new rows Knew / Vnew [B,H,Nq,d] into the caches at rows pos[b] .. (rows past
+        the capacity are dropped)."""
+        _hip.kv_cache_append(_torch_view(Knew), _torch_view(Vnew), _torch_view(Kc), _torch_view(Vc),
+                             HipKernelOps._i32(pos))

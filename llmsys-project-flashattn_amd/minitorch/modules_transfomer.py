@@ -127,11 +127,46 @@ class MultiHeadAttention(Module):
         result = result.permute(0, 2, 1, 3).contiguous()
         return result.view(batch_size, queries_len, self.n_embd)
 
-    def forward(self, x, kv_len=None):
+    def forward(self, x, kv_len=None, cache=None):
+        """cache: None (training / full forward), or this layer's slice of a KVCache (a
+        LayerKV; a one-layer KVCache is taken as its layer 0). With a cache the K / V rows of
+        x's tokens are appended at the cache's current lengths; an empty cache is a prefill
+        (today's causal flash attention over the prompt, kv_len = the prompt lengths of a
+        right-padded batch), otherwise x holds at most 8 new tokens per row and attends the
+        cache (Tensor.flash_attention_decode). The caller advances the cache's lengths once
+        every layer has run (DecoderLM.forward does)."""
         batch_size, seq_len, n_embd = x.shape
         q, k, kT, v = self.project_to_query_key_value(x)
-        attn = self.self_attention(q, k if self.use_flash_attention else kT, v, kv_len)
+        if cache is None:
+            attn = self.self_attention(q, k if self.use_flash_attention else kT, v, kv_len)
+        else:
+            attn = self._cached_attention(q, k, v, kv_len, cache)
         return self.out_projection(attn.view(batch_size * seq_len, n_embd)).view(batch_size, seq_len, n_embd)
+
+    def _cached_attention(self, q, k, v, kv_len, cache):
+        from .kv_cache import KVCache
+        if not self.use_flash_attention:
+            raise ValueError("a KV cache needs use_flash_attention=True")
+        if not self.causal:
+            raise ValueError("a KV cache needs causal attention")
+        lkv = cache.layer(0) if isinstance(cache, KVCache) else cache
+        kvc = lkv.cache
+        batch_size, num_head, seq_len, q_dim = q.shape
+        if (batch_size, num_head, q_dim) != (kvc.batch_size, kvc.n_head, kvc.head_dim):
+            raise ValueError(f"the KV cache was built for (B, H, d) = ({kvc.batch_size}, {kvc.n_head}, "
+                             f"{kvc.head_dim}), got ({batch_size}, {num_head}, {q_dim})")
+        prefill = kvc.empty
+        if not prefill and seq_len > 8:
+            raise ValueError(f"a decode step takes at most 8 new tokens per row, got {seq_len}")
+        if int(kvc.length_host.max()) + seq_len > kvc.n_positions:
+            raise ValueError(f"{seq_len} new tokens do not fit the KV cache ({kvc.n_positions} positions, "
+                             f"{int(kvc.length_host.max())} held)")
+        q.backend.kv_cache_append(k, v, lkv.k, lkv.v, kvc.length)
+        if prefill:
+            return self.self_attention(q, k, v, kv_len)
+        result = q.flash_attention_decode(lkv.k, lkv.v, kvc.visible(seq_len))
+        result = result.permute(0, 2, 1, 3).contiguous()
+        return result.view(batch_size, seq_len, self.n_embd)
 
 
 class FeedForward(Module):
@@ -176,10 +211,10 @@ class TransformerLayer(Module):
             self.ln_1 = LayerNorm1d(n_embd, ln_eps, backend)
             self.ln_2 = LayerNorm1d(n_embd, ln_eps, backend)
 
-    def forward(self, x, kv_len=None):
+    def forward(self, x, kv_len=None, cache=None):
         batch_size, seq_len, x_dim = x.shape
         a = self.ln_1(x.view(batch_size * seq_len, x_dim)).view(batch_size, seq_len, x_dim)
-        a = self.attention(a, kv_len) + x
+        a = (self.attention(a, kv_len) if cache is None else self.attention(a, kv_len, cache)) + x
         h = self.ln_2(a.view(batch_size * seq_len, x_dim)).view(batch_size, seq_len, x_dim)
         return self.ff(h) + a
 
@@ -204,12 +239,21 @@ class DecoderLM(Module):
         self.dropout = Dropout(p_dropout)
         self.lm_head = Linear(n_embd, n_vocab, bias, backend)
         self.use_fused_kernel = use_fused_kernel
+        self.use_flash_attention = use_flash_attention
+        self.n_positions = n_positions
+        self.n_head = n_head
         self.ln = FusedLayerNorm(n_embd, backend) if use_fused_kernel else LayerNorm1d(n_embd, ln_eps, backend)
 
-    def forward(self, idx, kv_len=None):
+    def forward(self, idx, kv_len=None, cache=None):
         """kv_len: optional valid-token count per batch row of a right-padded batch (keys past
         it are masked in every layer's self-attention; with the causal mask and right padding
-        this changes only the outputs at padding positions)."""
+        this changes only the outputs at padding positions).
+        cache: a KVCache (generation). The tokens of idx continue each row at cache.length[b]:
+        an empty cache is prefilled with the prompt (kv_len = the prompt lengths), afterwards
+        idx holds at most 8 new tokens per row. The cache's lengths advance by kv_len (prefill)
+        or by the number of tokens fed."""
+        if cache is not None:
+            return self._forward_cached(idx, kv_len, cache)
         batch_size, seq_len = idx.shape
         pos = _positions(seq_len, self.backend)
         h = self.token_embeddings(idx) + self.position_embeddings(pos).view(1, seq_len, self.n_embd)
@@ -218,3 +262,109 @@ class DecoderLM(Module):
             h = getattr(self, f"t_layer_{i + 1}")(h, kv_len)
         h = self.ln(h.view(batch_size * seq_len, self.n_embd))
         return self.lm_head(h).view(batch_size, seq_len, self.n_vocab)
+
+    def new_cache(self, batch_size: int):
+        """A KVCache for this model and a batch of batch_size rows."""
+        from .kv_cache import KVCache
+        return KVCache(self.n_layer, batch_size, self.n_head, self.n_positions, self.n_embd // self.n_head,
+                       self.backend)
+
+    def _forward_cached(self, idx, kv_len, cache):
+        if not self.use_flash_attention:
+            raise ValueError("a KV cache needs use_flash_attention=True")
+        batch_size, seq_len = idx.shape
+        if cache.n_layer != self.n_layer or cache.batch_size != batch_size:
+            raise ValueError(f"the KV cache was built for {cache.n_layer} layers and a batch of "
+                             f"{cache.batch_size}, got {self.n_layer} and {batch_size}")
+        prefill = cache.empty
+        if not prefill and seq_len > 8:
+            raise ValueError(f"a decode step takes at most 8 new tokens per row, got {seq_len}")
+        pos = cache.length_host[:, None] + np.arange(seq_len)[None, :]
+        if int(pos.max()) >= min(self.n_positions, cache.n_positions):
+            raise ValueError(f"position {int(pos.max())} is past n_positions = {self.n_positions}")
+        pos = tensor_from_numpy(np.ascontiguousarray(pos, dtype=datatype), backend=self.backend)
+        h = self.token_embeddings(idx) + self.position_embeddings(pos)
+        h = self.dropout(h)
+        for i in range(self.n_layer):
+            h = getattr(self, f"t_layer_{i + 1}")(h, kv_len, cache.layer(i))
+        h = self.ln(h.view(batch_size * seq_len, self.n_embd))
+        out = self.lm_head(h).view(batch_size, seq_len, self.n_vocab)
+        if prefill and kv_len is not None:
+            from .tensor import Tensor
+            held = kv_len.to_numpy() if isinstance(kv_len, Tensor) else kv_len
+            cache.advance(np.asarray(held, dtype=np.int64).reshape(batch_size))
+        else:
+            cache.advance(seq_len)
+        return out
+
+    def generate(self, prompts, max_new_tokens: int, eos_id=None, use_cache: bool = True):
+        """Greedy (argmax) decoding of a list of token-id lists, as the reference's generate
+        (project/run_machine_translation.py:271-328); returns the new ids per prompt (without
+        the eos that stopped a row). A row also stops once it holds more than n_positions tokens.
+        use_cache=False is the reference's loop, one prompt at a time with a full forward over
+        the whole prefix per token. use_cache=True right-pads the prompts into one batch,
+        prefills a KVCache once and then runs one decode step per token for the whole batch
+        (finished rows keep stepping; their outputs are discarded). The model is in eval()
+        for the call."""
+        prompts = [[int(t) for t in p] for p in prompts]
+        if not prompts or any(len(p) == 0 for p in prompts):
+            raise ValueError("generate needs at least one prompt and no empty prompt")
+        if max(len(p) for p in prompts) > self.n_positions:
+            raise ValueError(f"a prompt of {max(len(p) for p in prompts)} tokens is longer than "
+                             f"n_positions = {self.n_positions}")
+        was_training = self.training
+        self.eval()
+        try:
+            if use_cache:
+                return self._generate_cached(prompts, max_new_tokens, eos_id)
+            return [self._generate_plain(p, max_new_tokens, eos_id) for p in prompts]
+        finally:
+            if was_training:
+                self.train()
+
+    def _generate_plain(self, prompt, max_new_tokens, eos_id):
+        tokens, new = list(prompt), []
+        while len(new) < max_new_tokens and len(tokens) <= self.n_positions:
+            idx = tensor_from_numpy(np.asarray([tokens], dtype=datatype), backend=self.backend)
+            logits = self.forward(idx).to_numpy()
+            nxt = int(np.argmax(logits[0, len(tokens) - 1]))
+            if eos_id is not None and nxt == eos_id:
+                break
+            tokens.append(nxt)
+            new.append(nxt)
+        return new
+
+    def _generate_cached(self, prompts, max_new_tokens, eos_id):
+        B = len(prompts)
+        lens = np.array([len(p) for p in prompts], dtype=np.int64)
+        T = int(lens.max())
+        cache = self.new_cache(B)
+        idx = np.zeros((B, T), dtype=datatype)
+        for b, p in enumerate(prompts):
+            idx[b, :len(p)] = p
+        new = [[] for _ in range(B)]
+        done = np.zeros(B, dtype=bool)
+        if max_new_tokens <= 0:
+            return new
+        logits = self.forward(tensor_from_numpy(idx, backend=self.backend), kv_len=lens.astype(datatype),
+                              cache=cache).to_numpy()
+        last = logits[np.arange(B), lens - 1]
+        while True:
+            nxt = np.argmax(last, axis=-1)
+            for b in range(B):
+                if done[b]:
+                    continue
+                if eos_id is not None and int(nxt[b]) == eos_id:
+                    done[b] = True
+                    continue
+                new[b].append(int(nxt[b]))
+                # the row holds len(prompt) + len(new) tokens; past n_positions it cannot be fed
+                if len(new[b]) >= max_new_tokens or lens[b] + len(new[b]) > self.n_positions:
+                    done[b] = True
+            if done.all():
+                return new
+            # a finished row that filled its cache re-writes its last slot (its output is discarded)
+            if int(cache.length_host.max()) >= cache.n_positions:
+                cache.set_length(np.minimum(cache.length_host, cache.n_positions - 1))
+            step = tensor_from_numpy(nxt.astype(datatype).reshape(B, 1), backend=self.backend)
+            last = self.forward(step, cache=cache).to_numpy()[:, 0]

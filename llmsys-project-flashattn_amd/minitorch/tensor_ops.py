@@ -128,3 +128,6 @@ class TensorBackend:
         self.flash_attention_bw = ops.flash_attention_bw
         self.flash_attention_causal_fw = ops.flash_attention_causal_fw
         self.flash_attention_causal_bw = ops.flash_attention_causal_bw
+        # generation (optional: a backend without the decode kernels has no KV cache)
+        self.flash_attention_decode = getattr(ops, "flash_attention_decode", None)
+        self.kv_cache_append = getattr(ops, "kv_cache_append", None)

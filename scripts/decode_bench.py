@@ -1,0 +1,159 @@
+"""Decode-attention and generation timings (writes profiles/decode_bench.json).
+
+Per shape (B, H, L, d) and dtype, alternated in one process and timed with device events:
+
+  decode   one mt_flash_attn_decode step at Nq = 1 against a full cache of L rows
+           ([B, L, H, d] storage, the KVCache layout), caller-provided workspace
+  copy     a device-to-device copy of the same K and V bytes: the bandwidth this box reaches
+           on those bytes, the yardstick for the decode step's bytes/s
+  full     flash_fwd(causal=True) at N = L: what one generation step's attention costs
+           without a cache (a full causal forward over the prefix)
+
+The decode and copy legs rotate over enough cache copies to exceed the 256 MiB Infinity Cache,
+so that both read HBM (a single 134 MB cache would be served from that cache on every call
+after the first). Algorithmic bytes of the decode step: 2 B H L d esize for K and V, plus Q, O
+and the split workspace written once and read once.
+
+End to end: DecoderLM.generate tokens/s at config-5 width (V = 10000, E = 256, 8 heads,
+4 layers), cached against uncached (the reference's loop), at n_positions 40 and 1024.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "llmsys-project-flashattn_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+SHAPES = [(8, 16, 4096, 64, "bf16"), (8, 16, 4096, 64, "f32"), (1, 16, 16384, 128, "bf16"),
+          (64, 8, 40, 32, "f32")]
+ICACHE = 256 << 20
+
+
+def _timed(torch, fn, inner):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for i in range(inner):
+        fn(i)
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e-3 / inner
+
+
+def bench_shape(torch, _hip, B, H, L, d, name, rounds, warmup):
+    dt = torch.bfloat16 if name == "bf16" else torch.float32
+    es = 2 if name == "bf16" else 4
+    code = 1 if name == "bf16" else 0
+    kv_bytes = 2 * B * H * L * d * es
+    nset = min(8, max(2, -(-2 * ICACHE // kv_bytes) + 1))  # small caches: launch-bound, a few sets do
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rnd = lambda *s: torch.randn(*s, generator=g, device="cuda", dtype=torch.float32).to(dt)  # noqa: E731
+    caches = [(rnd(B, L, H, d).permute(0, 2, 1, 3), rnd(B, L, H, d).permute(0, 2, 1, 3)) for _ in range(nset)]
+    dst = (torch.empty_like(caches[0][0]), torch.empty_like(caches[0][1]))
+    q = rnd(B, 1, H, d).permute(0, 2, 1, 3)
+    kvl = torch.full((B,), L, dtype=torch.int32, device="cuda")
+    o = torch.empty((B, 1, H, d), dtype=dt, device="cuda").permute(0, 2, 1, 3)
+    m, l = (torch.empty((B, H, 1), dtype=torch.float32, device="cuda") for _ in range(2))
+    nsplit, span, tile = _hip.decode_splits(code, B, H, 1, L, d)
+    ws_bytes = _hip.decode_workspace_bytes(code, B, H, 1, L, d)
+    ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device="cuda") if ws_bytes else None
+    Q, K, V = (rnd(B, H, L, d) for _ in range(3))
+    O = torch.empty_like(Q)
+    M, Lw = (torch.empty((B, H, L), dtype=torch.float32, device="cuda") for _ in range(2))
+
+    def decode(i):
+        kc, vc = caches[i % nset]
+        _hip.flash_decode(q, kc, vc, kv_len=kvl, causal=True, out=o, m=m, l=l, workspace=ws)
+
+    def copy(i):
+        kc, vc = caches[i % nset]
+        dst[0].copy_(kc)
+        dst[1].copy_(vc)
+
+    def full(i):
+        _hip.flash_fwd(Q, K, V, True, out=O, m=M, l=Lw)
+    legs = {"decode": (decode, 4 * nset), "copy": (copy, 2 * nset), "full": (full, 2)}
+    for fn, inner in legs.values():
+        for _ in range(warmup):
+            _timed(torch, fn, inner)
+    times = {k: [] for k in legs}
+    for _ in range(rounds):  # the legs alternate inside every round
+        for k, (fn, inner) in legs.items():
+            times[k].append(_timed(torch, fn, inner))
+    alg_bytes = kv_bytes + 2 * B * H * d * es + 2 * ws_bytes
+    med = {k: statistics.median(v) for k, v in times.items()}
+    return {
+        "shape": [B, H, L, d], "dtype": name, "nq": 1, "splits": nsplit, "span_keys": span, "tile_keys": tile,
+        "workspace_bytes": ws_bytes, "kv_bytes": kv_bytes, "decode_algorithmic_bytes": alg_bytes,
+        "cache_sets_rotated": nset, "rounds": rounds,
+        "decode_s_median": med["decode"], "decode_s_min": min(times["decode"]),
+        "copy_s_median": med["copy"], "copy_s_min": min(times["copy"]),
+        "full_causal_fwd_s_median": med["full"], "full_causal_fwd_s_min": min(times["full"]),
+        "decode_bytes_per_s": alg_bytes / med["decode"],
+        "copy_read_bytes_per_s": kv_bytes / med["copy"],      # bytes read (as many are written)
+        "copy_moved_bytes_per_s": 2 * kv_bytes / med["copy"],  # read + written
+        "decode_vs_copy_read_rate": (alg_bytes / med["decode"]) / (kv_bytes / med["copy"]),
+        "full_over_decode": med["full"] / med["decode"],
+    }
+
+
+def bench_generate(minitorch, n_positions, prompt_len, new_tokens, batch, rounds):
+    np.random.seed(0)
+    backend = minitorch.TensorBackend(minitorch.HipKernelOps)
+    lm = minitorch.DecoderLM(n_vocab=10000, n_embd=256, n_head=8, n_positions=n_positions, p_dropout=0.0,
+                             backend=backend, use_fused_kernel=True, use_flash_attention=True)
+    rng = np.random.default_rng(0)
+    prompts = [[int(t) for t in rng.integers(0, 10000, prompt_len)] for _ in range(batch)]
+    legs = {"cached_batch": lambda: lm.generate(prompts, new_tokens, use_cache=True),
+            "cached_one": lambda: lm.generate(prompts[:1], new_tokens, use_cache=True),
+            "uncached_one": lambda: lm.generate(prompts[:1], new_tokens, use_cache=False)}
+    out = {k: fn() for k, fn in legs.items()}  # warm-up; the legs must agree
+    same = out["cached_one"] == out["uncached_one"] and out["cached_batch"][0] == out["cached_one"][0]
+    rate = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            toks = fn()  # ends in a device-to-host copy of the last logits: synchronised
+            rate[k].append(sum(len(t) for t in toks) / (time.perf_counter() - t0))
+    return {"n_positions": n_positions, "prompt_len": prompt_len, "new_tokens": new_tokens, "batch": batch,
+            "rounds": rounds, "legs_agree": bool(same),
+            **{f"{k}_tokens_per_s_median": statistics.median(v) for k, v in rate.items()},
+            **{f"{k}_tokens_per_s_best": max(v) for k, v in rate.items()}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "decode_bench.json"))
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--skip-generate", action="store_true")
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("decode_bench.py needs an MI355X (no timing is taken on a CPU)")
+    import minitorch
+    from minitorch import _hip
+    res = {"device": torch.cuda.get_device_name(0), "kernels": [], "generate": []}
+    for B, H, L, d, name in SHAPES:
+        r = bench_shape(torch, _hip, B, H, L, d, name, args.rounds, args.warmup)
+        print(json.dumps(r), flush=True)
+        res["kernels"].append(r)
+        torch.cuda.empty_cache()
+    if not args.skip_generate:
+        for npos, plen, new, batch, rounds in ((40, 8, 32, 8, 3), (1024, 768, 128, 8, 2)):
+            r = bench_generate(minitorch, npos, plen, new, batch, rounds)
+            print(json.dumps(r), flush=True)
+            res["generate"].append(r)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
