@@ -149,6 +149,38 @@ int mt_kv_cache_append(int dtype, const void* k_new, const void* v_new, void* k_
                        const int64_t* kcache_strides, const int64_t* vcache_strides,
                        const int* pos, void* stream);
 
+/* ---- generation: the next token chosen on the device ------------------------
+ * One id per row of the fp32 logits [B, V] (rows row_stride >= V elements apart, unit-stride
+ * columns; what lies between the rows is never read). Stream-ordered, allocates nothing, does
+ * not synchronise, capturable in a hipGraph. V <= 32768 (the kernel holds one row in LDS).
+ *   temperature == 0 (greedy): the lowest index that holds the row's maximum; a NaN counts as
+ *     the maximum and the first NaN wins (np.argmax).
+ *   temperature > 0 (sampling): the kept set K is the top_k largest entries under the order
+ *     (fp32 value descending, index ascending; -0 == +0), every entry when top_k <= 0 or
+ *     top_k >= V. p_i = exp((x_i - max_K x) / T) / sum over K. u is the value
+ *     mt_rand_uniform(out, B, seed) writes at index b. The id is the first i in K, in index
+ *     order, whose running sum of p over K exceeds u (the comparison is made on the unnormalised
+ *     sums against u times their total), the last index of K with p > 0 if rounding leaves
+ *     none (never an entry of p = 0, such as a -inf logit or an underflowed exp). Entries of
+ *     -inf have p = 0. A row whose maximum is not finite (a NaN, +inf, or every entry -inf)
+ *     takes the greedy id. top_k == 1 therefore equals greedy.
+ *   Every sum has a fixed order: the id is a function of the row's bits, T, top_k, the seed and
+ *   b alone, whatever else is in the batch.
+ * seed_dev != NULL: the seed is read from that device uint64 when the kernel runs (a captured
+ * step whose seed advances on the device); `seed` is then ignored.
+ * Outputs, written with plain stores: next_f32[b] = id as a float (the token ids minitorch
+ * feeds mt_embedding_fw) and / or next_i32[b] = id (either may be NULL, not both);
+ * done (NULL or [B], in/out): done[b] |= (id == eos_id), never cleared; eos_id < 0: no eos;
+ * history (NULL or [B] rows of history_stride ints; needs step_dev): history[b * history_stride
+ * + *step_dev] = id, *step_dev a device int32 read when the kernel runs; a step outside
+ * [0, history_stride) writes nothing.
+ * Refused with a status before any device call: B or V <= 0, V > 32768, row_stride < V, a
+ * negative or NaN temperature, NULL logits, both outputs NULL, history without step_dev. */
+int mt_select_token(const float* logits, int64_t B, int64_t V, int64_t row_stride, float temperature,
+                    int64_t top_k, uint64_t seed, const uint64_t* seed_dev, int64_t eos_id,
+                    float* next_f32, int32_t* next_i32, int32_t* done, int32_t* history,
+                    int64_t history_stride, const int32_t* step_dev, void* stream);
+
 /* ---- FlashAttention, reference-compatible host pointers (fp32) ------------ */
 /* reference src/flashattention_kernel.cu:259 */
 void launch_flashattention_forward(float* Q, float* K, float* V, float* O, float* l, float* m,

@@ -27,6 +27,7 @@
 
 #include "../../include/minitorch_hip.h"
 #include "fa_common.h"
+#include "rng.h"
 
 namespace mt {
 
@@ -1009,18 +1010,12 @@ using namespace mt;
 
 // ---- counter-based uniform RNG ---------------------------------------------------------
 // u[i] = top 24 bits of splitmix64(seed + golden·(i+1)) / 2^24, in [0, 1). Stateless: a
-// launch is reproducible from (seed, n) and any element is independent of the grid.
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-
+// launch is reproducible from (seed, n) and any element is independent of the grid. The hash
+// itself (mix64, uniform24) is rng.h, shared with mt_select_token.
 __global__ void rand_uniform_kernel(float* out, int64_t n, uint64_t seed) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t h = mix64(seed + 0x9e3779b97f4a7c15ull * (uint64_t)(i + 1));
-    out[i] = (float)(h >> 40) * (1.0f / 16777216.0f);
+    out[i] = uniform24(seed, i);
   }
 }
 
@@ -1073,8 +1068,7 @@ __global__ __launch_bounds__(256) void dropout_kernel(float* __restrict__ out, c
   if (seedp) seed = *seedp;
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
-    const uint64_t h = mix64(seed + 0x9e3779b97f4a7c15ull * (uint64_t)(i + 1));
-    const float u = (float)(h >> 40) * (1.0f / 16777216.0f);
+    const float u = uniform24(seed, i);
     out[i] = u > p ? x[i] * scale : 0.f;
   }
 }

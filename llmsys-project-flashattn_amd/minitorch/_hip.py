@@ -58,6 +58,8 @@ _PROTOS = {
                                     _i64p, _i64p, _i64p, _i64p, _vp, _vp, _i64, _vp]),
     "mt_kv_cache_append": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                   _i64p, _i64p, _i64p, _i64p, _vp, _vp]),
+    "mt_select_token": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _i64, ctypes.c_uint64, _vp, _i64,
+                               _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "mt_attn_softmax_fw": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64p, _int, _vp]),
     "mt_attn_softmax_bw": (_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "mt_layernorm_fw": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
@@ -395,6 +397,66 @@ def kv_cache_append(k_new, v_new, k_cache, v_cache, pos, stream: Optional[int] =
         dtype_code(k_new), k_new.data_ptr(), v_new.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
         B, H, Nq, Nmax, d, strides3(k_new), strides3(v_new), strides3(k_cache), strides3(v_cache),
         p.data_ptr(), st), "mt_kv_cache_append")
+
+
+def rand_uniform(n: int, seed: int, out=None, stream: Optional[int] = None):
+    """n draws of U[0,1) on the device (mt_rand_uniform: the counter-based hash of (seed, index));
+    returns the fp32 [n] tensor (`out` when given: dense, n elements)."""
+    torch = _torch()
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device="cuda")
+    if not out.is_cuda or out.dtype != torch.float32 or out.numel() != n or not out.is_contiguous():
+        raise ValueError(f"rand_uniform: out must be a contiguous device float32 tensor of {n} elements")
+    st = stream_ptr(out.device) if stream is None else stream
+    check(lib().mt_rand_uniform(out.data_ptr(), n, int(seed) & 0xFFFFFFFFFFFFFFFF, st), "mt_rand_uniform")
+    return out
+
+
+def select_token(logits, temperature: float = 0.0, top_k: int = 0, seed: int = 0, seed_dev=None, eos_id=None,
+                 out=None, out_i32=None, done=None, history=None, step_dev=None, stream: Optional[int] = None):
+    """The next token id of every row of logits (mt_select_token): a 2-D fp32 device view [B, V]
+    with a unit-stride last dim and any row stride >= V (e.g. ``logits3d[:, -1]``, no copy).
+    temperature 0: greedy (np.argmax's id); > 0: a draw from softmax(logits / temperature) over
+    the top_k largest entries (0: all), with u the value rand_uniform writes at index b for
+    `seed`. seed_dev: a device int64 [1] holding the seed instead (read when the kernel runs).
+    Returns (out, out_i32): fp32 [B] and int32 [B] ids, allocated when not given. done: int32 [B]
+    in/out, done[b] |= (id == eos_id). history: int32 [B, S] with step_dev an int32 [1] on the
+    device: history[b, step_dev[0]] = id."""
+    torch = _torch()
+    _check_dev(logits)
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"select_token takes a 2-D float32 [B, V] view, got {tuple(logits.shape)} {logits.dtype}")
+    B, V = logits.shape
+    if V > 1 and logits.stride(1) != 1:
+        raise ValueError("select_token: the vocabulary dimension must be unit-stride")
+    row_stride = logits.stride(0) if B > 1 else max(V, logits.stride(0))
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=logits.device)
+    if out_i32 is None:
+        out_i32 = torch.empty(B, dtype=torch.int32, device=logits.device)
+    for name, t, dt, n in (("out", out, torch.float32, B), ("out_i32", out_i32, torch.int32, B),
+                           ("done", done, torch.int32, B), ("step_dev", step_dev, torch.int32, 1),
+                           ("seed_dev", seed_dev, torch.int64, 1)):
+        if t is not None and (not t.is_cuda or t.dtype != dt or t.numel() != n or not t.is_contiguous()):
+            raise ValueError(f"select_token: {name} must be a contiguous device {dt} tensor of {n} element(s)")
+    hs = 0
+    if history is not None:
+        if (not history.is_cuda or history.dtype != torch.int32 or history.dim() != 2 or history.shape[0] != B
+                or history.stride(1) != 1):
+            raise ValueError(f"select_token: history must be a device int32 [{B}, S] tensor with unit-stride rows")
+        if step_dev is None:
+            raise ValueError("select_token: history needs step_dev")
+        # rows of S slots: a step at or past S is dropped by the kernel
+        hs = history.shape[1]
+        if B > 1 and history.stride(0) != hs:
+            raise ValueError("select_token: history rows must be contiguous")
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    st = stream_ptr(logits.device) if stream is None else stream
+    check(lib().mt_select_token(
+        logits.data_ptr(), B, V, row_stride, float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF,
+        ptr(seed_dev), -1 if eos_id is None else int(eos_id), out.data_ptr(), out_i32.data_ptr(), ptr(done),
+        ptr(history), hs, ptr(step_dev), st), "mt_select_token")
+    return out, out_i32
 
 
 def scratch_bytes() -> int:

@@ -27,6 +27,7 @@ a device value, a host-side constant created for the first time) fails loudly du
 run it once more in the warm-up, or keep it out of the step."""
 from __future__ import annotations
 
+import gc
 from typing import Any, Callable, List, Optional
 
 import numpy as np
@@ -79,6 +80,11 @@ class StepGraph:
                 step_fn()
         torch.cuda.current_stream().wait_stream(self.stream)
         self.graph = torch.cuda.CUDAGraph()
+        # dead Python cycles go now, as torch.cuda.graph did before a capture until torch 2.10:
+        # one that holds device objects (another StepGraph, say) and is collected while this
+        # stream captures would free them inside the capture. (Inferred from one abort with the
+        # collector running inside a capture; one collection per capture.)
+        gc.collect()
         global _CAPTURING
         _CAPTURING = self
         try:

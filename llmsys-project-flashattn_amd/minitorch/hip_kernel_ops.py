@@ -523,3 +523,20 @@ class HipKernelOps(TensorOps):
         the capacity are dropped)."""
         _hip.kv_cache_append(_torch_view(Knew), _torch_view(Vnew), _torch_view(Kc), _torch_view(Vc),
                              HipKernelOps._i32(pos))
+
+    @staticmethod
+    def select_token(logits: Tensor, temperature: float = 0.0, top_k: int = 0, seed: int = 0, rows=None, **kw):
+        """The next token ids chosen on the device (mt_select_token) from logits [B, V], or from
+        one position of logits [B, T, V]: the last (read in place, no copy), or position rows[b]
+        of batch row b (a prefill of right-padded prompts; the B rows are gathered first).
+        Returns (ids fp32 [B], ids int32 [B]) as torch device tensors; the keywords (seed_dev,
+        eos_id, out, out_i32, done, history, step_dev: torch device tensors) are _hip.select_token's."""
+        import torch
+        v = _torch_view(logits)
+        if v.dim() == 3:
+            if rows is None:
+                v = v[:, -1]
+            else:
+                r = torch.as_tensor(np.asarray(rows, dtype=np.int64), device=v.device)
+                v = v[torch.arange(v.shape[0], device=v.device), r]
+        return _hip.select_token(v, temperature, top_k, seed, **kw)

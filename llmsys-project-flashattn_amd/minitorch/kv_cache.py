@@ -79,6 +79,21 @@ class KVCache:
             self._visible = (n_new, self.length + n_new)
         return self._visible[1]
 
+    def clamp_to_last_slot(self) -> None:
+        """Rows that filled the cache step back to its last slot, on the device (stream-ordered,
+        capturable) and in the host mirror: what a one-token step does first, so that a finished
+        row that filled its cache re-writes its last slot (its output is discarded)."""
+        self.length.clamp_(max=self.n_positions - 1)
+        np.minimum(self.length_host, self.n_positions - 1, out=self.length_host)
+        self._visible = None
+
+    def mirror_step(self) -> None:
+        """The host mirror of one replayed one-token step (clamp_to_last_slot, then one token
+        appended): the captured step does the same on the device, nothing is copied."""
+        np.minimum(self.length_host, self.n_positions - 1, out=self.length_host)
+        self.length_host += 1
+        self._visible = None
+
     def advance(self, n_new) -> None:
         """Count n_new appended tokens (an int, or one count per batch row)."""
         a = np.broadcast_to(np.asarray(n_new, dtype=np.int64), (self.batch_size,))

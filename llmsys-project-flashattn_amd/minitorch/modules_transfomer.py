@@ -13,6 +13,8 @@ MultiHeadAttention from TransformerLayer and DecoderLM by keyword (reference :30
 """
 from __future__ import annotations
 
+import weakref
+
 import numpy as np
 
 from .module import Module
@@ -222,6 +224,12 @@ class TransformerLayer(Module):
 class DecoderLM(Module):
     """Decoder-only pre-LN LM with 4 TransformerLayers (reference :365-470)."""
 
+    # generate(graph=True) keeps device memory on the model: per batch size one KVCache and
+    # up to MAX_DECODE_GRAPHS captured steps (one per temperature / top_k / eos_id), for the
+    # MAX_DECODE_BATCH_SIZES most recently used batch sizes; drop_decode_graphs() frees it all
+    MAX_DECODE_GRAPHS = 4
+    MAX_DECODE_BATCH_SIZES = 4
+
     def __init__(self, n_vocab: int, n_embd: int, n_head: int, n_positions: int,
                  p_dropout: float = 0.1, ln_eps: float = 1e-5, bias: bool = True, backend=None,
                  use_fused_kernel: bool = False, use_flash_attention: bool = False, n_layer: int = 4):
@@ -243,6 +251,7 @@ class DecoderLM(Module):
         self.n_positions = n_positions
         self.n_head = n_head
         self.ln = FusedLayerNorm(n_embd, backend) if use_fused_kernel else LayerNorm1d(n_embd, ln_eps, backend)
+        self.graph_captures = 0  # hipGraph captures of the decode step (generate(graph=True))
 
     def forward(self, idx, kv_len=None, cache=None):
         """kv_len: optional valid-token count per batch row of a right-padded batch (keys past
@@ -297,44 +306,87 @@ class DecoderLM(Module):
             cache.advance(seq_len)
         return out
 
-    def generate(self, prompts, max_new_tokens: int, eos_id=None, use_cache: bool = True):
-        """Greedy (argmax) decoding of a list of token-id lists, as the reference's generate
+    def generate(self, prompts, max_new_tokens: int, eos_id=None, use_cache: bool = True,
+                 temperature: float = 0.0, top_k: int = 0, seed=None, graph: bool = False, sync_every: int = 8):
+        """Decoding of a list of token-id lists, as the reference's generate
         (project/run_machine_translation.py:271-328); returns the new ids per prompt (without
         the eos that stopped a row). A row also stops once it holds more than n_positions tokens.
         use_cache=False is the reference's loop, one prompt at a time with a full forward over
         the whole prefix per token. use_cache=True right-pads the prompts into one batch,
         prefills a KVCache once and then runs one decode step per token for the whole batch
         (finished rows keep stepping; their outputs are discarded). The model is in eval()
-        for the call."""
+        for the call.
+
+        temperature == 0 (default) is greedy (argmax) decoding. temperature > 0 samples from
+        softmax(logits / temperature) over the top_k largest logits (0: all of them), on the
+        device (mt_select_token; a backend without the kernel raises): step t of the call draws
+        with seed + t and the uniform draw of batch row b (use_cache=False runs every prompt as
+        row 0 of its own batch, so its draws differ from the batched legs'). seed=None takes one
+        seed from NumPy's global generator (np.random.seed reproduces a run, as for dropout).
+
+        graph=True (needs use_cache=True and the select_token kernel): the prompt is prefilled
+        and the first token chosen eagerly; every further token is one replay of a captured
+        hipGraph of the whole step (positions from the cache's device lengths, the token chosen
+        and recorded on the device), with no copy to or from the host. The host reads the `done`
+        flags every sync_every replays to stop early once every row is finished, and the token
+        history once at the end; the returned ids do not depend on sync_every. The graph stays on
+        the model, with the KVCache of its batch size, for the next call with the same batch
+        size, temperature, top_k, eos_id (held by value in the captured launches) and parameter
+        storage (held by address: Parameter.update re-captures); graph_captures counts the
+        captures. At most MAX_DECODE_GRAPHS graphs per batch size and MAX_DECODE_BATCH_SIZES
+        batch sizes are kept (least recently used go first); drop_decode_graphs() frees them."""
         prompts = [[int(t) for t in p] for p in prompts]
         if not prompts or any(len(p) == 0 for p in prompts):
             raise ValueError("generate needs at least one prompt and no empty prompt")
         if max(len(p) for p in prompts) > self.n_positions:
             raise ValueError(f"a prompt of {max(len(p) for p in prompts)} tokens is longer than "
                              f"n_positions = {self.n_positions}")
+        temperature = float(temperature)
+        if not temperature >= 0.0:
+            raise ValueError(f"temperature must be >= 0, got {temperature}")
+        if graph and not use_cache:
+            raise ValueError("generate(graph=True) replays the cached decode step: it needs use_cache=True")
+        sampler = None
+        if temperature > 0.0 or graph:
+            if getattr(self.backend, "select_token", None) is None:
+                raise ValueError("sampling and graph=True choose tokens on the device: they need a backend "
+                                 "with the select_token kernel (HipKernelOps)")
+            if temperature == 0.0:
+                seed = 0  # greedy: never read, and NumPy's generator is left where it was
+            elif seed is None:
+                seed = int(np.random.randint(0, 2**63 - 1, dtype=np.int64))
+            sampler = (temperature, int(top_k), int(seed))
         was_training = self.training
         self.eval()
         try:
+            if graph:
+                return self._generate_graph(prompts, max_new_tokens, eos_id, sampler, max(1, int(sync_every)))
+            if temperature == 0.0:
+                sampler = None
             if use_cache:
-                return self._generate_cached(prompts, max_new_tokens, eos_id)
-            return [self._generate_plain(p, max_new_tokens, eos_id) for p in prompts]
+                return self._generate_cached(prompts, max_new_tokens, eos_id, sampler)
+            return [self._generate_plain(p, max_new_tokens, eos_id, sampler) for p in prompts]
         finally:
             if was_training:
                 self.train()
 
-    def _generate_plain(self, prompt, max_new_tokens, eos_id):
+    def _generate_plain(self, prompt, max_new_tokens, eos_id, sampler=None):
         tokens, new = list(prompt), []
         while len(new) < max_new_tokens and len(tokens) <= self.n_positions:
             idx = tensor_from_numpy(np.asarray([tokens], dtype=datatype), backend=self.backend)
-            logits = self.forward(idx).to_numpy()
-            nxt = int(np.argmax(logits[0, len(tokens) - 1]))
+            if sampler is None:
+                logits = self.forward(idx).to_numpy()
+                nxt = int(np.argmax(logits[0, len(tokens) - 1]))
+            else:
+                nxt = int(self.backend.select_token(self.forward(idx), sampler[0], sampler[1],
+                                                    sampler[2] + len(new))[1].cpu().numpy()[0])
             if eos_id is not None and nxt == eos_id:
                 break
             tokens.append(nxt)
             new.append(nxt)
         return new
 
-    def _generate_cached(self, prompts, max_new_tokens, eos_id):
+    def _generate_cached(self, prompts, max_new_tokens, eos_id, sampler=None):
         B = len(prompts)
         lens = np.array([len(p) for p in prompts], dtype=np.int64)
         T = int(lens.max())
@@ -346,11 +398,18 @@ class DecoderLM(Module):
         done = np.zeros(B, dtype=bool)
         if max_new_tokens <= 0:
             return new
-        logits = self.forward(tensor_from_numpy(idx, backend=self.backend), kv_len=lens.astype(datatype),
-                              cache=cache).to_numpy()
-        last = logits[np.arange(B), lens - 1]
+
+        def choose(logits, rows, t):
+            # rows: the position per batch row whose logits decide (None: the only one)
+            if sampler is None:
+                host = logits.to_numpy()
+                return np.argmax(host[np.arange(B), rows] if rows is not None else host[:, 0], axis=-1)
+            return self.backend.select_token(logits, sampler[0], sampler[1], sampler[2] + t,
+                                             rows=rows)[1].cpu().numpy()
+        nxt = choose(self.forward(tensor_from_numpy(idx, backend=self.backend), kv_len=lens.astype(datatype),
+                                  cache=cache), lens - 1, 0)
+        t = 0
         while True:
-            nxt = np.argmax(last, axis=-1)
             for b in range(B):
                 if done[b]:
                     continue
@@ -367,4 +426,162 @@ class DecoderLM(Module):
             if int(cache.length_host.max()) >= cache.n_positions:
                 cache.set_length(np.minimum(cache.length_host, cache.n_positions - 1))
             step = tensor_from_numpy(nxt.astype(datatype).reshape(B, 1), backend=self.backend)
-            last = self.forward(step, cache=cache).to_numpy()[:, 0]
+            t += 1
+            nxt = choose(self.forward(step, cache=cache), None, t)
+
+    # ---- the decode step that never touches the host, and its graph -----------------------
+    def _device_step(self, st: "_DecodeState") -> None:
+        """One new token per row with nothing from the host: positions from the cache's device
+        lengths (rows that filled the cache step back to its last slot first), the token ids
+        from the buffer the previous select_token wrote; append, decode attention and the
+        cache's advance as in _forward_cached; then select_token writes the next ids, ORs
+        `done` and stores into history[b, step], and the step counter and the seed advance by
+        one on the device. Capturable: no to_numpy(), no tensor_from_numpy, no host constant."""
+        import torch
+        from .tensor import Tensor
+        from .tensor_data import TensorData
+        cache, B = st.cache, st.cache.batch_size
+        cache.clamp_to_last_slot()
+        pos = Tensor(TensorData(cache.length.to(torch.float32), (B, 1)), backend=self.backend)
+        h = self.token_embeddings(st.ids) + self.position_embeddings(pos)
+        h = self.dropout(h)
+        for i in range(self.n_layer):
+            h = getattr(self, f"t_layer_{i + 1}")(h, None, cache.layer(i))
+        h = self.ln(h.view(B, self.n_embd))
+        logits = self.lm_head(h)
+        cache.advance(1)
+        self.backend.select_token(logits, st.temperature, st.top_k, seed_dev=st.seed, eos_id=st.eos_id,
+                                  out=st.ids_dev, out_i32=st.ids_i32, done=st.done, history=st.history,
+                                  step_dev=st.step)
+        st.step.add_(1)
+        st.seed.add_(1)
+
+    def drop_decode_graphs(self) -> None:
+        """Free the KV caches and captured graphs generate(graph=True) keeps on the model (the
+        next such call captures again)."""
+        self.__dict__.pop("_decode_graphs", None)
+
+    def _generate_graph(self, prompts, max_new_tokens, eos_id, sampler, sync_every):
+        from .graphs import StepGraph
+        if not self.use_flash_attention:
+            raise ValueError("a KV cache needs use_flash_attention=True")
+        B = len(prompts)
+        lens = np.array([len(p) for p in prompts], dtype=np.int64)
+        new = [[] for _ in range(B)]
+        if max_new_tokens <= 0:
+            return new
+        temperature, top_k, seed = sampler
+        graphs = self.__dict__.setdefault("_decode_graphs", {})
+        entry = graphs.pop(B, None)
+        if entry is None:
+            # per batch size: the buffers (one KVCache) and the graphs captured over them; the
+            # last MAX_DECODE_BATCH_SIZES batch sizes are kept
+            while len(graphs) >= self.MAX_DECODE_BATCH_SIZES:
+                graphs.pop(next(iter(graphs)))
+            entry = {"state": _DecodeState(self, B), "graphs": {}}
+        graphs[B] = entry  # most recently used last
+        st = entry["state"]
+        st.begin(temperature, top_k, eos_id, seed)
+        # eager: the prefill (the prompt length varies) and the first token
+        T = int(lens.max())
+        idx = np.zeros((B, T), dtype=datatype)
+        for b, p in enumerate(prompts):
+            idx[b, :len(p)] = p
+        logits = self.forward(tensor_from_numpy(idx, backend=self.backend), kv_len=lens.astype(datatype),
+                              cache=st.cache)
+        self.backend.select_token(logits, temperature, top_k, rows=lens - 1, seed_dev=st.seed, eos_id=st.eos_id,
+                                  out=st.ids_dev, out_i32=st.ids_i32, done=st.done, history=st.history,
+                                  step_dev=st.step)
+        st.step.add_(1)
+        st.seed.add_(1)
+        # tokens row b can still return: max_new_tokens, or until it holds more than n_positions
+        limit = np.minimum(max_new_tokens, self.n_positions - lens + 1)
+        total = int(limit.max())
+        steps = 1
+        step_graph = None
+        if total > 1:
+            # the captured launches hold the sampling arguments by value (one graph per set of
+            # them, the last MAX_DECODE_GRAPHS kept) and the parameters by address
+            args = (temperature, top_k, st.eos_id)
+            params = tuple(p.value._tensor.data_ptr() for p in self.parameters())
+            held = entry["graphs"].pop(args, None)
+            if held is not None and held[1] == params:
+                step_graph = held[0]
+            else:
+                held = None  # a stale graph's memory goes first
+                while len(entry["graphs"]) >= self.MAX_DECODE_GRAPHS:
+                    entry["graphs"].pop(next(iter(entry["graphs"])))
+                saved = st.snapshot()
+                # the graph must die with the model, by reference count: a model <-> step-function
+                # cycle would leave the hipGraph to the cyclic collector, which may run inside
+                # somebody else's stream capture, where destroying a graph is not allowed
+                me = weakref.ref(self)
+                step_graph = StepGraph(lambda: me()._device_step(st), warmup=2)  # warm-ups: real steps
+                st.restore(saved)
+                self.graph_captures = (self.graph_captures or 0) + 1
+            entry["graphs"][args] = (step_graph, params)  # most recently used last
+        while steps < total:
+            step_graph.replay()
+            st.cache.mirror_step()
+            steps += 1
+            if eos_id is not None and (steps - 1) % sync_every == 0:
+                fin = st.done.cpu().numpy().astype(bool) | (steps >= limit)
+                if fin.all():
+                    break
+        hist = st.history[:, :steps].cpu().numpy()
+        for b in range(B):
+            for tok in hist[b]:
+                if eos_id is not None and int(tok) == eos_id:
+                    break
+                new[b].append(int(tok))
+                if len(new[b]) >= max_new_tokens or lens[b] + len(new[b]) > self.n_positions:
+                    break
+        return new
+
+
+class _DecodeState:
+    """The device buffers of DecoderLM's captured decode step, for one batch size: the KVCache,
+    the token ids the next step feeds (fp32, what mt_embedding_fw reads, and int32), the `done`
+    flags, the token history [B, n_positions] (no row returns more tokens than that), the step
+    counter and the seed slot."""
+
+    def __init__(self, lm: DecoderLM, batch_size: int):
+        import torch
+        from .tensor import Tensor
+        from .tensor_data import TensorData
+        self.cache = lm.new_cache(batch_size)
+        self.ids_dev = torch.zeros(batch_size, dtype=torch.float32, device="cuda")
+        self.ids = Tensor(TensorData(self.ids_dev, (batch_size, 1)), backend=lm.backend)
+        self.ids_i32 = torch.zeros(batch_size, dtype=torch.int32, device="cuda")
+        self.done = torch.zeros(batch_size, dtype=torch.int32, device="cuda")
+        self.history = torch.zeros((batch_size, lm.n_positions), dtype=torch.int32, device="cuda")
+        self.step = torch.zeros(1, dtype=torch.int32, device="cuda")
+        self.seed = torch.zeros(1, dtype=torch.int64, device="cuda")
+        self.temperature, self.top_k, self.eos_id = 0.0, 0, None
+
+    def begin(self, temperature, top_k, eos_id, seed: int) -> None:
+        """A new call: an empty cache, no row done, step 0, the call's seed."""
+        self.temperature, self.top_k = temperature, top_k
+        self.eos_id = None if eos_id is None else int(eos_id)
+        self.cache.reset()
+        self.done.zero_()
+        self.step.zero_()
+        seed &= 0xFFFFFFFFFFFFFFFF
+        self.seed.fill_(seed - (1 << 64) if seed >> 63 else seed)  # the uint64's bits as int64
+
+    def snapshot(self):
+        c = self.cache
+        return (c.length.clone(), c.length_host.copy(), self.ids_dev.clone(), self.ids_i32.clone(),
+                self.done.clone(), self.step.clone(), self.seed.clone())
+
+    def restore(self, saved) -> None:
+        c = self.cache
+        length, length_host, ids, ids_i32, done, step, seed = saved
+        c.length.copy_(length)
+        c.length_host[:] = length_host
+        c._visible = None
+        self.ids_dev.copy_(ids)
+        self.ids_i32.copy_(ids_i32)
+        self.done.copy_(done)
+        self.step.copy_(step)
+        self.seed.copy_(seed)

@@ -131,3 +131,5 @@ class TensorBackend:
         # generation (optional: a backend without the decode kernels has no KV cache)
         self.flash_attention_decode = getattr(ops, "flash_attention_decode", None)
         self.kv_cache_append = getattr(ops, "kv_cache_append", None)
+        # the next token chosen on the device (optional: a backend without it keeps the host argmax)
+        self.select_token = getattr(ops, "select_token", None)

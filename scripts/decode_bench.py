@@ -16,6 +16,15 @@ and the split workspace written once and read once.
 
 End to end: DecoderLM.generate tokens/s at config-5 width (V = 10000, E = 256, 8 heads,
 4 layers), cached against uncached (the reference's loop), at n_positions 40 and 1024.
+
+--graph-legs instead writes profiles/generate_graph_bench.json (decode_bench.json is left alone):
+
+  generate      the same two rows with generate(graph=True) (the captured decode step, tokens
+                chosen on the device) beside the cached-eager and uncached legs, batch 1 and 8,
+                greedy, and one sampled graph leg (T = 0.8, top_k = 50); host clock around calls
+                that end in a device-to-host copy; the legs alternate inside every round
+  select_token  mt_select_token alone at (B, V) = (8, 10000) and (64, 10000): greedy, top_k = 50
+                and the whole vocabulary at T = 1, device events around 64 launches, alternated
 """
 import argparse
 import json
@@ -127,9 +136,82 @@ def bench_generate(minitorch, n_positions, prompt_len, new_tokens, batch, rounds
             **{f"{k}_tokens_per_s_best": max(v) for k, v in rate.items()}}
 
 
+def bench_generate_graph(minitorch, n_positions, prompt_len, new_tokens, batch, rounds):
+    np.random.seed(0)
+    backend = minitorch.TensorBackend(minitorch.HipKernelOps)
+    lm = minitorch.DecoderLM(n_vocab=10000, n_embd=256, n_head=8, n_positions=n_positions, p_dropout=0.0,
+                             backend=backend, use_fused_kernel=True, use_flash_attention=True)
+    rng = np.random.default_rng(0)
+    prompts = [[int(t) for t in rng.integers(0, 10000, prompt_len)] for _ in range(batch)]
+    sample = dict(temperature=0.8, top_k=50, seed=1)
+    legs = {"graph_one": lambda: lm.generate(prompts[:1], new_tokens, graph=True),
+            "cached_one": lambda: lm.generate(prompts[:1], new_tokens, use_cache=True),
+            "uncached_one": lambda: lm.generate(prompts[:1], new_tokens, use_cache=False),
+            "graph_batch": lambda: lm.generate(prompts, new_tokens, graph=True),
+            "cached_batch": lambda: lm.generate(prompts, new_tokens, use_cache=True),
+            "graph_batch_sampled": lambda: lm.generate(prompts, new_tokens, graph=True, **sample),
+            "cached_batch_sampled": lambda: lm.generate(prompts, new_tokens, use_cache=True, **sample)}
+    out = {k: fn() for k, fn in legs.items()}  # warm-up (captures the graphs); the legs must agree
+    same = (out["graph_one"] == out["cached_one"] == out["uncached_one"] and out["graph_batch"] == out["cached_batch"]
+            and out["graph_batch_sampled"] == out["cached_batch_sampled"])
+    captures = lm.graph_captures
+    rate = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            toks = fn()  # every leg ends in a device-to-host copy: synchronised
+            rate[k].append(sum(len(t) for t in toks) / (time.perf_counter() - t0))
+    med = {k: statistics.median(v) for k, v in rate.items()}
+    return {"n_positions": n_positions, "prompt_len": prompt_len, "new_tokens": new_tokens, "batch": batch,
+            "rounds": rounds, "legs_agree": bool(same), "graph_captures": captures,
+            "recaptured_while_timing": lm.graph_captures != captures,
+            **{f"{k}_tokens_per_s_median": v for k, v in med.items()},
+            **{f"{k}_tokens_per_s_best": max(v) for k, v in rate.items()},
+            "graph_over_cached_one": med["graph_one"] / med["cached_one"],
+            "graph_over_cached_batch": med["graph_batch"] / med["cached_batch"]}
+
+
+def bench_select(torch, _hip, B, V, rounds, warmup, inner=64):
+    g = torch.Generator(device="cuda").manual_seed(0)
+    logits = 3.0 * torch.randn(B, V, generator=g, device="cuda", dtype=torch.float32)
+    out = torch.empty(B, dtype=torch.float32, device="cuda")
+    out_i = torch.empty(B, dtype=torch.int32, device="cuda")
+    kinds = {"greedy": dict(temperature=0.0), "top_k_50": dict(temperature=1.0, top_k=50),
+             "whole_vocabulary": dict(temperature=1.0, top_k=0)}
+    legs = {k: (lambda i, kw=kw: _hip.select_token(logits, seed=i, out=out, out_i32=out_i, **kw)) for k, kw in kinds.items()}
+    for fn in legs.values():
+        for _ in range(warmup):
+            _timed(torch, fn, inner)
+    times = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():
+            times[k].append(_timed(torch, fn, inner))
+    return {"B": B, "V": V, "rounds": rounds, "launches_per_timing": inner, "row_bytes": 4 * V,
+            **{f"{k}_s_median": statistics.median(v) for k, v in times.items()},
+            **{f"{k}_s_min": min(v) for k, v in times.items()}}
+
+
+def graph_legs(args, torch, minitorch, _hip):
+    res = {"device": torch.cuda.get_device_name(0), "select_token": [], "generate": []}
+    for B, V in ((8, 10000), (64, 10000)):
+        r = bench_select(torch, _hip, B, V, args.rounds, args.warmup)
+        print(json.dumps(r), flush=True)
+        res["select_token"].append(r)
+    for npos, plen, new, batch, rounds in ((40, 8, 32, 8, 5), (1024, 768, 128, 8, 3)):
+        r = bench_generate_graph(minitorch, npos, plen, new, batch, rounds)
+        print(json.dumps(r), flush=True)
+        res["generate"].append(r)
+    os.makedirs(os.path.dirname(args.graph_out), exist_ok=True)
+    with open(args.graph_out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "decode_bench.json"))
+    ap.add_argument("--graph-legs", action="store_true",
+                    help="run the generate(graph=True) and select_token legs instead, into --graph-out")
+    ap.add_argument("--graph-out", default=os.path.join(ROOT, "profiles", "generate_graph_bench.json"))
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--skip-generate", action="store_true")
@@ -139,6 +221,8 @@ def main():
         raise SystemExit("decode_bench.py needs an MI355X (no timing is taken on a CPU)")
     import minitorch
     from minitorch import _hip
+    if args.graph_legs:
+        return graph_legs(args, torch, minitorch, _hip)
     res = {"device": torch.cuda.get_device_name(0), "kernels": [], "generate": []}
     for B, H, L, d, name in SHAPES:
         r = bench_shape(torch, _hip, B, H, L, d, name, args.rounds, args.warmup)
