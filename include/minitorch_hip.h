@@ -140,6 +140,28 @@ int mt_flash_attn_decode(int dtype, int causal, const void* q, const void* k_cac
                          int64_t d, const int64_t* q_strides, const int64_t* k_strides,
                          const int64_t* v_strides, const int64_t* o_strides, const int* kv_len,
                          void* workspace, int64_t workspace_bytes, void* stream);
+/* Grouped-query decode: H query heads share Hkv key / value heads in groups of G = H / Hkv
+ * (Hkv = 1: multi-query); query head h reads kv head h / G.
+ *   q, o:              [B, H, Nq, d]
+ *   k_cache, v_cache:  [B, Hkv, Nk, d] (NULL strides: dense [B, Hkv, Nk, d])
+ *   m, l:              fp32 [B*H*Nq], indexed by query head
+ * Row packing: one workgroup serves one kv head and gs = min(G, 8 / Nq) query heads of its
+ * group, Nq queries each (its row r is head hkv*G + slice*gs + r / Nq, query r % Nq), so a
+ * group's K and V are read ceil(G / gs) times per step instead of G times. The workspace is laid
+ * out as above, per (b, query head, query, split): B*H*Nq*splits*(d+2)*4 bytes, 0 with one split.
+ * The split count and span are those mt_flash_attn_decode_splits gives for (dtype, B, H, Nq, Nk,
+ * d), whatever Hkv (a packed workgroup streams the keys a plain one does), never of kv_len.
+ * Hkv == H is mt_flash_attn_decode: the same plan, launches and bits. Refused before any device
+ * call: Hkv <= 0, Hkv > H, H % Hkv != 0, and whatever mt_flash_attn_decode refuses. */
+int mt_flash_attn_decode_gqa_splits(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk,
+                                    int64_t d, int64_t* span_keys, int64_t* tile_keys);
+int64_t mt_flash_attn_decode_gqa_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq,
+                                                 int64_t Nk, int64_t d);
+int mt_flash_attn_decode_gqa(int dtype, int causal, const void* q, const void* k_cache, const void* v_cache,
+                             void* o, float* m, float* l, int64_t B, int64_t H, int64_t Hkv, int64_t Nq,
+                             int64_t Nk, int64_t d, const int64_t* q_strides, const int64_t* k_strides,
+                             const int64_t* v_strides, const int64_t* o_strides, const int* kv_len,
+                             void* workspace, int64_t workspace_bytes, void* stream);
 /* Copies the Nq new K and V rows of every (b, h) ([B, H, Nq, d]) into the caches
  * ([B, H, Nmax, d]) at rows pos[b] .. pos[b] + Nq - 1 (pos: device int32 [B]); rows outside
  * [0, Nmax) are dropped and nothing else in the caches is written. 16-B rows as above. */

@@ -1,5 +1,6 @@
-// C ABI of the KV-cache decode path (include/minitorch_hip.h): mt_flash_attn_decode and its
-// split / workspace queries, mt_kv_cache_append. Kernels: fa_decode.hip. Every argument is
+// C ABI of the KV-cache decode path (include/minitorch_hip.h): mt_flash_attn_decode[_gqa] and
+// their split / workspace queries, mt_kv_cache_append. The plain entry points are the Hkv = H
+// case of the grouped-query ones. Kernels: fa_decode.hip. Every argument is
 // validated before the first device call, as the other mt_flash_attn_* entry points do.
 #include "../../include/minitorch_hip.h"
 #include "fa_decode.h"
@@ -7,12 +8,14 @@
 
 namespace mt {
 // dtype, sizes and the 16-B row rule on d; 0 or the error status
-static int decode_sizes(int dtype, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t d) {
+static int decode_sizes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d) {
   if (dtype != MT_F32 && dtype != MT_BF16 && dtype != MT_BF16_F32OUT)
     return set_error("unsupported dtype %d", dtype);
   if (B <= 0 || H <= 0 || Nk <= 0 || d <= 0)
     return set_error("bad sizes B=%lld H=%lld Nk=%lld d=%lld", (long long)B, (long long)H,
                      (long long)Nk, (long long)d);
+  if (Hkv <= 0 || Hkv > H || H % Hkv)
+    return set_error("kv heads must divide the query heads (H=%lld, Hkv=%lld)", (long long)H, (long long)Hkv);
   if (Nq < 1 || Nq > 8)
     return set_error("decode takes 1 to 8 query rows per head (Nq=%lld)", (long long)Nq);
   if (d > 256) return set_error("decode head dim out of range (d=%lld; d <= 256)", (long long)d);
@@ -50,28 +53,29 @@ using namespace mt;
 
 extern "C" {
 
-int mt_flash_attn_decode_splits(int dtype, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t d,
-                                int64_t* span_keys, int64_t* tile_keys) {
-  if (decode_sizes(dtype, B, H, Nq, Nk, d)) return 0;
-  const DecodePlan p = decode_plan(dtype == MT_F32 ? 4 : 2, B, H, Nq, Nk, d);
+int mt_flash_attn_decode_gqa_splits(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d,
+                                    int64_t* span_keys, int64_t* tile_keys) {
+  if (decode_sizes(dtype, B, H, Hkv, Nq, Nk, d)) return 0;
+  const DecodePlan p = decode_plan(dtype == MT_F32 ? 4 : 2, B, H, Hkv, Nq, Nk, d);
   if (span_keys) *span_keys = p.span;
   if (tile_keys) *tile_keys = p.tile;
   return p.nsplit;
 }
 
-int64_t mt_flash_attn_decode_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t d) {
-  if (decode_sizes(dtype, B, H, Nq, Nk, d)) return -1;
-  return decode_ws_bytes(decode_plan(dtype == MT_F32 ? 4 : 2, B, H, Nq, Nk, d), B, H, Nq, d);
+int64_t mt_flash_attn_decode_gqa_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk,
+                                                 int64_t d) {
+  if (decode_sizes(dtype, B, H, Hkv, Nq, Nk, d)) return -1;
+  return decode_ws_bytes(decode_plan(dtype == MT_F32 ? 4 : 2, B, H, Hkv, Nq, Nk, d), B, H, Nq, d);
 }
 
-int mt_flash_attn_decode(int dtype, int causal, const void* q, const void* k_cache, const void* v_cache,
-                         void* o, float* m, float* l, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t d,
-                         const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                         const int64_t* o_strides, const int* kv_len,
-                         void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = decode_sizes(dtype, B, H, Nq, Nk, d)) return rc;
+int mt_flash_attn_decode_gqa(int dtype, int causal, const void* q, const void* k_cache, const void* v_cache,
+                             void* o, float* m, float* l, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk,
+                             int64_t d, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                             const int64_t* o_strides, const int* kv_len,
+                             void* workspace, int64_t workspace_bytes, void* stream) {
+  if (int rc = decode_sizes(dtype, B, H, Hkv, Nq, Nk, d)) return rc;
   const int esize = dtype == MT_F32 ? 4 : 2, osize = dtype == MT_BF16 ? 2 : 4;
-  const DecodePlan p = decode_plan(esize, B, H, Nq, Nk, d);
+  const DecodePlan p = decode_plan(esize, B, H, Hkv, Nq, Nk, d);
   const int64_t need = decode_ws_bytes(p, B, H, Nq, d);
   if (need > 0 && (!workspace || workspace_bytes < need))
     return set_error("decode workspace too small: %lld bytes, mt_flash_attn_decode_workspace_bytes gives %lld",
@@ -81,17 +85,36 @@ int mt_flash_attn_decode(int dtype, int causal, const void* q, const void* k_cac
   a.q = q; a.k = k_cache; a.v = v_cache; a.o = o; a.m = m; a.l = l;
   a.ws = (float*)workspace; a.kv_len = kv_len;
   strides_or_dense(a.qs, q_strides, H, Nq, d);
-  strides_or_dense(a.ks, k_strides, H, Nk, d);
-  strides_or_dense(a.vs, v_strides, H, Nk, d);
+  strides_or_dense(a.ks, k_strides, Hkv, Nk, d);
+  strides_or_dense(a.vs, v_strides, Hkv, Nk, d);
   strides_or_dense(a.os, o_strides, H, Nq, d);
   if (int rc = aligned16("q", q, a.qs, esize)) return rc;
   if (int rc = aligned16("k_cache", k_cache, a.ks, esize)) return rc;
   if (int rc = aligned16("v_cache", v_cache, a.vs, esize)) return rc;
   if (int rc = aligned16("o", o, a.os, osize)) return rc;
   a.H = (int)H; a.Nq = (int)Nq; a.Nk = (int)Nk; a.d = (int)d;
+  a.Hkv = (int)Hkv; a.gs = p.gs; a.slices = p.slices; a.rows = B * H * Nq;
   a.nsplit = p.nsplit; a.span = p.span; a.causal = causal != 0; a.o_f32 = osize == 4;
   a.scale_log2 = (float)(1.4426950408889634 / sqrt((double)d));
   return check_hip(launch_decode(a, esize == 2, B, (hipStream_t)stream), "mt_flash_attn_decode");
+}
+
+int mt_flash_attn_decode_splits(int dtype, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t d,
+                                int64_t* span_keys, int64_t* tile_keys) {
+  return mt_flash_attn_decode_gqa_splits(dtype, B, H, H, Nq, Nk, d, span_keys, tile_keys);
+}
+
+int64_t mt_flash_attn_decode_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t d) {
+  return mt_flash_attn_decode_gqa_workspace_bytes(dtype, B, H, H, Nq, Nk, d);
+}
+
+int mt_flash_attn_decode(int dtype, int causal, const void* q, const void* k_cache, const void* v_cache,
+                         void* o, float* m, float* l, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t d,
+                         const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                         const int64_t* o_strides, const int* kv_len,
+                         void* workspace, int64_t workspace_bytes, void* stream) {
+  return mt_flash_attn_decode_gqa(dtype, causal, q, k_cache, v_cache, o, m, l, B, H, H, Nq, Nk, d, q_strides,
+                                  k_strides, v_strides, o_strides, kv_len, workspace, workspace_bytes, stream);
 }
 
 int mt_kv_cache_append(int dtype, const void* k_new, const void* v_new, void* k_cache, void* v_cache,

@@ -5,7 +5,8 @@
 // waves, so K and V rows go straight from global memory to VGPRs with 16-B loads (no LDS
 // staging) and the products run on the VALU in fp32.
 //
-// Pass 1, fa_decode_partial: grid (B*H, splits), 4 waves per workgroup. A key row is C = d *
+// Pass 1, fa_decode_partial: grid (B*Hkv*slices, splits), 4 waves per workgroup (Hkv = H, one
+// slice: grid (B*H, splits); grouped queries below). A key row is C = d *
 // esize / 16 chunks of 16 B; LPK = the power of two >= C (at least 4) lanes share one key, a
 // lane owning one chunk, so one wave-wide load covers 64 / LPK keys and a wave takes kUnroll
 // such loads of K and of V per step (tile_keys = kUnroll * 64 / LPK keys; with NQ <= 4 query
@@ -23,8 +24,16 @@
 // Pass 2, fa_decode_combine: one 64-thread workgroup per (b, h, query) merges the splits in
 // index order (rescale to the largest m, sum l and O, normalise): a fixed order, bit-reproducible.
 //
-// The split count and span are a host function of (dtype, B, H, Nq, Nk, d) only
-// (decode_plan), never of kv_len: a captured launch replays as the cache fills.
+// Grouped queries (Hkv < H, G = H / Hkv): query head h reads kv head h / G. The up to 8 register
+// rows of a workgroup are independent of each other, so they hold gs = min(G, 8 / Nq) heads of
+// one group, Nq queries each: row r is head hkv*G + slice*gs + r / Nq, query r % Nq, and a
+// group takes slices = ceil(G / gs) workgroups per split, each reading the span's K/V once. A
+// row whose head is past the group (a ragged last slice) is a row past Nq: limit 0, no load, no
+// store. Q, O, m, l and the workspace stay addressed by query head; K and V by hkv.
+//
+// The plan is a host function of (dtype, B, H, Hkv, Nq, Nk, d) only (decode_plan; the split
+// count and span of B, H, Nk, d; the packing of Hkv and Nq), never of kv_len: a captured
+// launch replays as the cache fills.
 #include "fa_decode.h"
 #include <algorithm>
 
@@ -42,11 +51,20 @@ static int decode_lpk(int64_t d, int esize) {
   return l;
 }
 
-DecodePlan decode_plan(int esize, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t d) {
-  (void)Nq;
+DecodePlan decode_plan(int esize, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d) {
   DecodePlan p;
   p.lpk = decode_lpk(d, esize);
   p.tile = kDecUnroll * 64 / p.lpk;
+  const int64_t G = H / Hkv;
+  p.gs = (int)std::min<int64_t>(G, 8 / Nq);
+  p.slices = (int)((G + p.gs - 1) / p.gs);
+  // The span is sized by the query heads, B * H, whatever Hkv: a packed workgroup streams the
+  // keys a plain one does (for gs heads at once), the grid is B * Hkv * slices per split and
+  // the workspace and the combine are those of the plain plan. Sizing it by the B * Hkv *
+  // slices workgroups instead gives G times the splits at a small B * Hkv, and every split is
+  // one more workspace row per query for the combine's serial merge: at (1,16,16384,128) bf16,
+  // Hkv = 4, 256 splits took 111 us against 38 us with the plain plan's 64 (and 52 us for
+  // the plain kernel on the repeated K/V); DESIGN.md section 3, "Grouped-query decode".
   const int64_t bh = B * H;
   const int64_t want = std::max<int64_t>(1, (kDecTargetWgs + bh - 1) / bh);
   int64_t span = std::max<int64_t>((Nk + want - 1) / want, (int64_t)kDecWaves * p.tile);
@@ -114,8 +132,12 @@ __device__ __forceinline__ void store_o4(void* o, int o_f32, int64_t e, const fl
   }
 }
 
+// fp32, one row, d <= 64 sits at the 96-VGPR edge of 5 waves per SIMD: ask for them (the allocator
+// otherwise lands on 95-98 from one build to the next)
 template <typename T, int LPK, int NQ>
-__global__ __launch_bounds__(kDecWaves * 64) void fa_decode_partial(const DecodeArgs a) {
+__global__ __launch_bounds__(kDecWaves * 64)
+__attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 && NQ == 1 && LPK <= 16 ? 5 : 1)))
+void fa_decode_partial(const DecodeArgs a) {
   constexpr int EPC = Chunk<T>::N;       // elements per 16-B chunk
   constexpr int GROUPS = 64 / LPK;       // keys per wave-wide load
   constexpr int TILE = kDecUnroll * GROUPS;
@@ -123,8 +145,12 @@ __global__ __launch_bounds__(kDecWaves * 64) void fa_decode_partial(const Decode
   __shared__ float s_o[kDecWaves][NQ][DP];
   __shared__ float s_ml[kDecWaves][NQ][2];
 
-  const int split = blockIdx.y, bh = blockIdx.x;
-  const int b = bh / a.H, h = bh % a.H;
+  const int split = blockIdx.y;
+  const int bk = blockIdx.x / a.slices, slice = blockIdx.x - bk * a.slices;
+  const int b = bk / a.Hkv, hkv = bk - b * a.Hkv;
+  const int G = a.H / a.Hkv;
+  const int h0 = hkv * G + slice * a.gs;     // first query head of this workgroup
+  const int nh = min(a.gs, G - slice * a.gs);  // its heads (fewer in a ragged last slice)
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = lane % LPK, g = lane / LPK;
   const int C = a.d / EPC;               // real chunks per row (<= LPK)
@@ -135,20 +161,23 @@ __global__ __launch_bounds__(kDecWaves * 64) void fa_decode_partial(const Decode
   const int k0 = split * a.span;
   const int kend = min(k0 + a.span, n);
   const bool final_out = a.nsplit == 1;
-  const int64_t row0 = (int64_t)bh * a.Nq;  // first (b, h, query) row
+  const int64_t row0 = ((int64_t)b * a.H + h0) * a.Nq;  // first (b, h, query) row
 
   if (k0 < kend) {  // workgroup-uniform
     // visible-key limit per query (no key at or past it is admitted)
     int lim[NQ];
     float qf[NQ][EPC];
+    int hh = 0, qi = 0;  // register row i is head h0 + hh, query qi
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
-      lim[i] = (i < a.Nq) ? min(a.causal ? n - a.Nq + 1 + i : n, kend) : 0;
+      const bool row = NQ == 1 || hh < nh;  // nh >= 1
+      lim[i] = row ? min(a.causal ? n - a.Nq + 1 + qi : n, kend) : 0;
       uint4 u = make_uint4(0u, 0u, 0u, 0u);
-      if (i < a.Nq && c < C)
-        u = *(const uint4*)((const T*)a.q + (int64_t)b * a.qs[0] + (int64_t)h * a.qs[1] +
-                            (int64_t)i * a.qs[2] + c * EPC);
+      if (row && c < C)
+        u = *(const uint4*)((const T*)a.q + (int64_t)b * a.qs[0] + (int64_t)(h0 + hh) * a.qs[1] +
+                            (int64_t)qi * a.qs[2] + c * EPC);
       Chunk<T>::unpack(u, qf[i]);
+      if (++qi == a.Nq) { qi = 0; ++hh; }
     }
     float m[NQ], l[NQ], acc[NQ][EPC];
 #pragma unroll
@@ -158,8 +187,8 @@ __global__ __launch_bounds__(kDecWaves * 64) void fa_decode_partial(const Decode
 #pragma unroll
       for (int e = 0; e < EPC; ++e) acc[i][e] = 0.f;
     }
-    const T* kb = (const T*)a.k + (int64_t)b * a.ks[0] + (int64_t)h * a.ks[1];
-    const T* vb = (const T*)a.v + (int64_t)b * a.vs[0] + (int64_t)h * a.vs[1];
+    const T* kb = (const T*)a.k + (int64_t)b * a.ks[0] + (int64_t)hkv * a.ks[1];
+    const T* vb = (const T*)a.v + (int64_t)b * a.vs[0] + (int64_t)hkv * a.vs[1];
     const int cc = c < C ? c : 0;  // a lane past the row's chunks re-reads chunk 0 (values dropped)
 
     // the 16-B loads of one tile: K then V rows of kDecUnroll x GROUPS keys. Keys at or past kend
@@ -291,8 +320,9 @@ __global__ __launch_bounds__(kDecWaves * 64) void fa_decode_partial(const Decode
 
   // merge the waves (fixed order) and write this split's result, 4 O elements per thread
   const bool empty = !(k0 < kend);
-  for (int idx = tid; idx < a.Nq * d4; idx += kDecWaves * 64) {
-    const int i = idx / d4, e4 = idx - i * d4;
+  for (int idx = tid; idx < nh * a.Nq * d4; idx += kDecWaves * 64) {
+    const int i = idx / d4, e4 = idx - i * d4;  // register row i: head h0 + i / Nq, query i % Nq
+    const int hh = NQ == 1 ? 0 : i / a.Nq, qi = i - hh * a.Nq;
     float mx = -INFINITY, ls = 0.f;
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
     if (!empty) {
@@ -310,7 +340,7 @@ __global__ __launch_bounds__(kDecWaves * 64) void fa_decode_partial(const Decode
     if (final_out) {
       const float inv = ls > 0.f ? 1.f / ls : 0.f;
       o.x *= inv; o.y *= inv; o.z *= inv; o.w *= inv;
-      store_o4(a.o, a.o_f32, (int64_t)b * a.os[0] + (int64_t)h * a.os[1] + (int64_t)i * a.os[2] + 4 * e4, o);
+      store_o4(a.o, a.o_f32, (int64_t)b * a.os[0] + (int64_t)(h0 + hh) * a.os[1] + (int64_t)qi * a.os[2] + 4 * e4, o);
       if (e4 == 0) {
         if (a.m) a.m[row0 + i] = mx * kLn2;
         if (a.l) a.l[row0 + i] = ls;
@@ -319,7 +349,7 @@ __global__ __launch_bounds__(kDecWaves * 64) void fa_decode_partial(const Decode
       const int64_t r = (row0 + i) * a.nsplit + split;
       *(float4*)(a.ws + r * a.d + 4 * e4) = o;
       if (e4 == 0) {
-        float* ml = a.ws + (int64_t)gridDim.x * a.Nq * a.nsplit * a.d + 2 * r;
+        float* ml = a.ws + a.rows * a.nsplit * a.d + 2 * r;
         ml[0] = mx;
         ml[1] = ls;
       }
@@ -360,8 +390,9 @@ __global__ __launch_bounds__(64) void fa_decode_combine(const DecodeArgs a) {
 }
 
 template <typename T, int LPK> static hipError_t launch_partial_nq(const DecodeArgs& a, dim3 grid, hipStream_t st) {
-  if (a.Nq == 1) fa_decode_partial<T, LPK, 1><<<grid, kDecWaves * 64, 0, st>>>(a);
-  else if (a.Nq <= 4) fa_decode_partial<T, LPK, 4><<<grid, kDecWaves * 64, 0, st>>>(a);
+  const int rows = a.gs * a.Nq;  // register rows of a workgroup
+  if (rows == 1) fa_decode_partial<T, LPK, 1><<<grid, kDecWaves * 64, 0, st>>>(a);
+  else if (rows <= 4) fa_decode_partial<T, LPK, 4><<<grid, kDecWaves * 64, 0, st>>>(a);
   else fa_decode_partial<T, LPK, 8><<<grid, kDecWaves * 64, 0, st>>>(a);
   return hipGetLastError();
 }
@@ -379,10 +410,11 @@ template <typename T> static hipError_t launch_partial(const DecodeArgs& a, int 
   return hipErrorInvalidValue;
 }
 
-// Sizes are validated by the caller (capi_decode.hip): 1 <= Nq <= 8, d <= 256, 16-B rows.
+// Sizes are validated by the caller (capi_decode.hip): 1 <= Nq <= 8, d <= 256, 16-B rows,
+// Hkv divides H, gs / slices / rows from decode_plan.
 hipError_t launch_decode(const DecodeArgs& a, bool bf16_in, int64_t B, hipStream_t st) {
   const int lpk = decode_lpk(a.d, bf16_in ? 2 : 4);
-  const dim3 grid((unsigned)(B * a.H), (unsigned)a.nsplit);
+  const dim3 grid((unsigned)(B * a.Hkv * a.slices), (unsigned)a.nsplit);
   hipError_t e = bf16_in ? launch_partial<bf16>(a, lpk, grid, st) : launch_partial<float>(a, lpk, grid, st);
   if (e != hipSuccess || a.nsplit == 1) return e;
   fa_decode_combine<<<dim3((unsigned)(B * a.H * a.Nq)), 64, 0, st>>>(a);

@@ -56,6 +56,10 @@ _PROTOS = {
     "mt_flash_attn_decode_workspace_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64]),
     "mt_flash_attn_decode": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                     _i64p, _i64p, _i64p, _i64p, _vp, _vp, _i64, _vp]),
+    "mt_flash_attn_decode_gqa_splits": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64p, _i64p]),
+    "mt_flash_attn_decode_gqa_workspace_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64, _i64]),
+    "mt_flash_attn_decode_gqa": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
+                                        _i64p, _i64p, _i64p, _i64p, _vp, _vp, _i64, _vp]),
     "mt_kv_cache_append": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                   _i64p, _i64p, _i64p, _i64p, _vp, _vp]),
     "mt_select_token": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _i64, ctypes.c_uint64, _vp, _i64,
@@ -326,19 +330,21 @@ def _decode_code(q, out, out_dtype) -> int:
     return code
 
 
-def decode_splits(dtype: int, B: int, H: int, Nq: int, Nk: int, d: int):
-    """(splits, span_keys, tile_keys) of mt_flash_attn_decode at these sizes (dtype: an MT_*
+def decode_splits(dtype: int, B: int, H: int, Nq: int, Nk: int, d: int, Hkv: Optional[int] = None):
+    """(splits, span_keys, tile_keys) of mt_flash_attn_decode[_gqa] at these sizes (dtype: an MT_*
     code): how many workgroups share the keys of one (batch, head), the keys each takes and the
-    keys one wave takes per inner step. A function of the sizes only."""
+    keys one wave takes per inner step. A function of the sizes only. Hkv: the caches' heads
+    (None: H)."""
     span, tile = ctypes.c_int64(0), ctypes.c_int64(0)
-    n = lib().mt_flash_attn_decode_splits(dtype, B, H, Nq, Nk, d, ctypes.byref(span), ctypes.byref(tile))
+    n = lib().mt_flash_attn_decode_gqa_splits(dtype, B, H, H if Hkv is None else Hkv, Nq, Nk, d,
+                                              ctypes.byref(span), ctypes.byref(tile))
     if n <= 0:
         raise ValueError(lib().mt_last_error().decode(errors="replace"))
     return n, span.value, tile.value
 
 
-def decode_workspace_bytes(dtype: int, B: int, H: int, Nq: int, Nk: int, d: int) -> int:
-    n = lib().mt_flash_attn_decode_workspace_bytes(dtype, B, H, Nq, Nk, d)
+def decode_workspace_bytes(dtype: int, B: int, H: int, Nq: int, Nk: int, d: int, Hkv: Optional[int] = None) -> int:
+    n = lib().mt_flash_attn_decode_gqa_workspace_bytes(dtype, B, H, H if Hkv is None else Hkv, Nq, Nk, d)
     if n < 0:
         raise ValueError(lib().mt_last_error().decode(errors="replace"))
     return int(n)
@@ -346,16 +352,19 @@ def decode_workspace_bytes(dtype: int, B: int, H: int, Nq: int, Nk: int, d: int)
 
 def flash_decode(q, k_cache, v_cache, kv_len=None, causal: bool = True, out=None, m=None, l=None,
                  workspace=None, out_dtype=None, stream: Optional[int] = None):
-    """Decode attention (mt_flash_attn_decode): q [B,H,Nq,d] (Nq <= 8, the last Nq positions of
-    each row) against the caches [B,H,Nk,d] (any strides with unit-stride d), of which the first
-    kv_len[b] rows are visible (None: all Nk). Returns (O, m, l); m, l fp32 [B,H,Nq]. workspace:
-    a device buffer of at least decode_workspace_bytes (allocated when None)."""
+    """Decode attention (mt_flash_attn_decode_gqa): q [B,H,Nq,d] (Nq <= 8, the last Nq positions
+    of each row) against the caches [B,Hkv,Nk,d] (any strides with unit-stride d; Hkv divides H,
+    query head h reads kv head h // (H // Hkv)), of which the first kv_len[b] rows are visible
+    (None: all Nk). Returns (O, m, l); m, l fp32 [B,H,Nq]. workspace: a device buffer of at least
+    decode_workspace_bytes (allocated when None)."""
     torch = _torch()
     _check_dev(q, k_cache, v_cache)
     B, H, Nq, d = q.shape
-    Nk = k_cache.shape[2]
-    if k_cache.shape != (B, H, Nk, d) or v_cache.shape != k_cache.shape:
+    Hkv, Nk = k_cache.shape[1], k_cache.shape[2]
+    if k_cache.shape != (B, Hkv, Nk, d) or v_cache.shape != k_cache.shape:
         raise ValueError(f"cache shapes {tuple(k_cache.shape)} {tuple(v_cache.shape)} do not match q {tuple(q.shape)}")
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"the caches' {Hkv} heads do not divide q's {H} heads")
     if not (q.dtype == k_cache.dtype == v_cache.dtype):
         raise TypeError("q/k_cache/v_cache dtypes differ")
     code = _decode_code(q, out, out_dtype)
@@ -365,24 +374,25 @@ def flash_decode(q, k_cache, v_cache, kv_len=None, causal: bool = True, out=None
         m = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
     if l is None:
         l = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
-    need = lib().mt_flash_attn_decode_workspace_bytes(code, B, H, Nq, Nk, d)
+    need = lib().mt_flash_attn_decode_gqa_workspace_bytes(code, B, H, Hkv, Nq, Nk, d)
     if workspace is None and need > 0:
         workspace = torch.empty(need // 4, dtype=torch.float32, device=q.device)
     kv = _kv_arg(kv_len, B, q.device)
     st = stream_ptr(q.device) if stream is None else stream
-    check(lib().mt_flash_attn_decode(
+    check(lib().mt_flash_attn_decode_gqa(
         code, int(causal), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(),
-        m.data_ptr(), l.data_ptr(), B, H, Nq, Nk, d, strides3(q), strides3(k_cache), strides3(v_cache),
+        m.data_ptr(), l.data_ptr(), B, H, Hkv, Nq, Nk, d, strides3(q), strides3(k_cache), strides3(v_cache),
         strides3(out), None if kv is None else kv.data_ptr(),
         None if workspace is None else workspace.data_ptr(),
         0 if workspace is None else workspace.numel() * workspace.element_size(), st),
-        "mt_flash_attn_decode")
+        "mt_flash_attn_decode_gqa")
     return out, m, l
 
 
 def kv_cache_append(k_new, v_new, k_cache, v_cache, pos, stream: Optional[int] = None) -> None:
     """Copy the new rows k_new / v_new [B,H,Nq,d] into the caches [B,H,Nmax,d] at rows
-    pos[b] .. pos[b] + Nq - 1 (pos: [B] int32 on the device; rows past the capacity are dropped)."""
+    pos[b] .. pos[b] + Nq - 1 (pos: [B] int32 on the device; rows past the capacity are dropped).
+    H is the caches' head count (the kv heads of a grouped-query model)."""
     torch = _torch()
     _check_dev(k_new, v_new, k_cache, v_cache)
     B, H, Nq, d = k_new.shape

@@ -506,7 +506,7 @@ class HipKernelOps(TensorOps):
     @staticmethod
     def flash_attention_decode(Q: Tensor, Kc: Tensor, Vc: Tensor, kv_len=None, causal: bool = True) -> Tensor:
         """O [B,H,Nq,d] of the Nq <= 8 newest query rows against the caches Kc / Vc
-        [B,H,Nmax,d], of which the first kv_len[b] rows are visible (the queries are the last Nq
+        [B,Hkv,Nmax,d] (Hkv divides H: query head h reads kv head h // (H // Hkv)), of which the first kv_len[b] rows are visible (the queries are the last Nq
         of them). Inference only. O is laid out like Q's storage (as _flash_fw does)."""
         import torch
         B, H, Nq, d = Q.shape
@@ -519,8 +519,8 @@ class HipKernelOps(TensorOps):
 
     @staticmethod
     def kv_cache_append(Knew: Tensor, Vnew: Tensor, Kc: Tensor, Vc: Tensor, pos) -> None:
-        """Write the new rows Knew / Vnew [B,H,Nq,d] into the caches at rows pos[b] .. (rows past
-        the capacity are dropped)."""
+        """Write the new rows Knew / Vnew [B,Hkv,Nq,d] into the caches [B,Hkv,Nmax,d] at rows
+        pos[b] .. (rows past the capacity are dropped)."""
         _hip.kv_cache_append(_torch_view(Knew), _torch_view(Vnew), _torch_view(Kc), _torch_view(Vc),
                              HipKernelOps._i32(pos))
 

@@ -2,9 +2,10 @@
 
 A decode step then needs the new tokens' Q/K/V and one read of each layer's cache
 (``mt_flash_attn_decode``) instead of a full causal forward over the prefix. Per layer the cache
-holds K and V as ``[B, n_positions, H, d]`` storage (the layout ``MultiHeadAttention`` projects
-into), seen by the kernels as ``[B, H, n_positions, d]`` through strides; rows at or past
-``length[b]`` are uninitialised and never read.
+holds K and V as ``[B, n_positions, Hkv, d]`` storage (the layout ``MultiHeadAttention`` projects
+into), seen by the kernels as ``[B, Hkv, n_positions, d]`` through strides; rows at or past
+``length[b]`` are uninitialised and never read. ``Hkv = n_kv_head`` is the model's key / value
+heads: ``n_head`` unless the model uses grouped-query attention.
 """
 from __future__ import annotations
 
@@ -17,7 +18,7 @@ __all__ = ["KVCache", "LayerKV"]
 
 
 class LayerKV:
-    """One layer's K / V cache tensors ([B, H, n_positions, d] views) and the owning cache."""
+    """One layer's K / V cache tensors ([B, n_kv_head, n_positions, d] views) and the owning cache."""
 
     def __init__(self, cache: "KVCache", k: Tensor, v: Tensor):
         self.cache = cache
@@ -26,7 +27,8 @@ class LayerKV:
 
 
 class KVCache:
-    def __init__(self, n_layer: int, batch_size: int, n_head: int, n_positions: int, head_dim: int, backend):
+    def __init__(self, n_layer: int, batch_size: int, n_head: int, n_positions: int, head_dim: int, backend,
+                 n_kv_head=None):
         if getattr(backend, "flash_attention_decode", None) is None or getattr(backend, "kv_cache_append", None) is None:
             raise ValueError("KVCache needs a backend with the decode kernels (HipKernelOps)")
         if head_dim % 4 != 0 or head_dim > 256:
@@ -34,12 +36,17 @@ class KVCache:
                              "(fp32 rows must be a multiple of 16 bytes: head_dim % 4 == 0, head_dim <= 256)")
         if min(n_layer, batch_size, n_head, n_positions) <= 0:
             raise ValueError("KVCache: sizes must be positive")
+        if n_kv_head is None:
+            n_kv_head = n_head
+        if n_kv_head <= 0 or n_head % n_kv_head:
+            raise ValueError(f"KVCache: n_kv_head = {n_kv_head} does not divide n_head = {n_head}")
         import torch
-        self.n_layer, self.batch_size, self.n_head = n_layer, batch_size, n_head
+        self.n_layer, self.batch_size, self.n_head = n_layer, batch_size, n_head  # n_head: the query heads
+        self.n_kv_head = n_kv_head
         self.n_positions, self.head_dim, self.backend = n_positions, head_dim, backend
-        shape = (batch_size, n_head, n_positions, head_dim)
-        strides = (n_positions * n_head * head_dim, head_dim, n_head * head_dim, 1)
-        numel = batch_size * n_positions * n_head * head_dim
+        shape = (batch_size, n_kv_head, n_positions, head_dim)
+        strides = (n_positions * n_kv_head * head_dim, head_dim, n_kv_head * head_dim, 1)
+        numel = batch_size * n_positions * n_kv_head * head_dim
 
         def buf():
             return Tensor(TensorData(torch.empty(numel, dtype=torch.float32, device="cuda"), shape, strides),

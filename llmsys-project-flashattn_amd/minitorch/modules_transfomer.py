@@ -54,22 +54,39 @@ def _positions(seq_len: int, backend):
         t = _INDEX_CACHE[key] = tensor([[float(i) for i in range(seq_len)]], backend=backend)
     return t
 
+def _group_ones(group: int, backend):
+    key = ("ones", id(backend), group)
+    t = _INDEX_CACHE.get(key)
+    if t is None:
+        if len(_INDEX_CACHE) > 64:
+            _INDEX_CACHE.clear()
+        t = _INDEX_CACHE[key] = tensor_from_numpy(np.ones((1, 1, group, 1, 1), dtype=datatype), backend=backend)
+    return t
+
 datatype = np.float32
 
 
 class MultiHeadAttention(Module):
     def __init__(self, n_embd: int, n_head: int, causal: bool = False, p_dropout: float = 0.1,
                  bias: bool = True, backend=None, use_fused_kernel: bool = False,
-                 use_flash_attention: bool = False):
+                 use_flash_attention: bool = False, n_kv_head=None):
+        """n_kv_head: grouped-query attention. The n_head query heads share n_kv_head key / value
+        heads in groups of n_head // n_kv_head (query head h uses kv head h // group; 1 is
+        multi-query attention). None: n_head, every head its own K and V."""
         super().__init__()
+        if n_kv_head is None:
+            n_kv_head = n_head
+        if n_kv_head <= 0 or n_head % n_kv_head:
+            raise ValueError(f"n_kv_head = {n_kv_head} does not divide n_head = {n_head}")
         self.backend = backend
         self.n_embd = n_embd
         self.n_head = n_head
+        self.n_kv_head = n_kv_head
         self.causal = causal
         self.attn_hidden_dim = n_embd // n_head
         self.q_projection = Linear(n_embd, n_embd, bias, backend)
-        self.k_projection = Linear(n_embd, n_embd, bias, backend)
-        self.v_projection = Linear(n_embd, n_embd, bias, backend)
+        self.k_projection = Linear(n_embd, n_kv_head * self.attn_hidden_dim, bias, backend)
+        self.v_projection = Linear(n_embd, n_kv_head * self.attn_hidden_dim, bias, backend)
         self.out_projection = Linear(n_embd, n_embd, bias, backend)
         self.dropout = Dropout(p_dropout)
         self.use_fused_kernel = use_fused_kernel
@@ -84,12 +101,24 @@ class MultiHeadAttention(Module):
         batch_size, seq_len, n_embd = x.shape
         flat = x.view(batch_size * seq_len, n_embd)
         shp = (batch_size, seq_len, self.n_head, self.attn_hidden_dim)
+        kv_shp = (batch_size, seq_len, self.n_kv_head, self.attn_hidden_dim)
         q = self.q_projection(flat).view(*shp).permute(0, 2, 1, 3)
-        k4 = self.k_projection(flat).view(*shp)
+        k4 = self.k_projection(flat).view(*kv_shp)
         kT = k4.permute(0, 2, 3, 1)
         k = k4.permute(0, 2, 1, 3)
-        v = self.v_projection(flat).view(*shp).permute(0, 2, 1, 3)
+        v = self.v_projection(flat).view(*kv_shp).permute(0, 2, 1, 3)
         return q, k, kT, v
+
+    def _repeat_kv(self, x):
+        """[B, n_kv_head, a, b] -> [B, n_head, a, b], head h a copy of kv head h // group (the
+        order the decode kernel uses): a broadcast multiply by ones, whose backward sums the
+        group's gradients. There is no fused grouped-query training kernel."""
+        group = self.n_head // self.n_kv_head
+        if group == 1:
+            return x
+        batch_size, n_kv, a, b = x.shape
+        rep = x.contiguous().view(batch_size, n_kv, 1, a, b) * _group_ones(group, self.backend)
+        return rep.contiguous().view(batch_size, self.n_head, a, b)
 
     def create_padding_mask(self, kv_len, seq_len):
         """The reference's key-padding contract (src/softmax_kernel.cu:26-33: attn_mask
@@ -102,8 +131,10 @@ class MultiHeadAttention(Module):
         """``kT`` is the [B,H,d,N] transpose, or the [B,H,N,d] keys on the flash path.
         ``kv_len``: optional per-batch-row count of valid (non-padding) keys: the flash path
         masks keys >= kv_len[b] in the kernel (mt_flash_attn_*_varlen); the other branches add
-        the equivalent [B, to_len] padding mask."""
+        the equivalent [B, to_len] padding mask. With n_kv_head < n_head, kT and v hold
+        n_kv_head heads and are repeated to n_head first."""
         batch_size, num_head, queries_len, q_dim = q.shape
+        kT, v = self._repeat_kv(kT), self._repeat_kv(v)
         scale = self.attn_hidden_dim ** 0.5
         if self.use_flash_attention:
             kv = None if kv_len is None else _kv_tensor(kv_len, batch_size, self.backend)
@@ -135,7 +166,7 @@ class MultiHeadAttention(Module):
         x's tokens are appended at the cache's current lengths; an empty cache is a prefill
         (today's causal flash attention over the prompt, kv_len = the prompt lengths of a
         right-padded batch), otherwise x holds at most 8 new tokens per row and attends the
-        cache (Tensor.flash_attention_decode). The caller advances the cache's lengths once
+        cache (Tensor.flash_attention_decode; the cache holds n_kv_head heads). The caller advances the cache's lengths once
         every layer has run (DecoderLM.forward does)."""
         batch_size, seq_len, n_embd = x.shape
         q, k, kT, v = self.project_to_query_key_value(x)
@@ -154,9 +185,10 @@ class MultiHeadAttention(Module):
         lkv = cache.layer(0) if isinstance(cache, KVCache) else cache
         kvc = lkv.cache
         batch_size, num_head, seq_len, q_dim = q.shape
-        if (batch_size, num_head, q_dim) != (kvc.batch_size, kvc.n_head, kvc.head_dim):
-            raise ValueError(f"the KV cache was built for (B, H, d) = ({kvc.batch_size}, {kvc.n_head}, "
-                             f"{kvc.head_dim}), got ({batch_size}, {num_head}, {q_dim})")
+        if (batch_size, num_head, self.n_kv_head, q_dim) != (kvc.batch_size, kvc.n_head, kvc.n_kv_head, kvc.head_dim):
+            raise ValueError(f"the KV cache was built for (B, H, Hkv, d) = ({kvc.batch_size}, {kvc.n_head}, "
+                             f"{kvc.n_kv_head}, {kvc.head_dim}), got ({batch_size}, {num_head}, "
+                             f"{self.n_kv_head}, {q_dim})")
         prefill = kvc.empty
         if not prefill and seq_len > 8:
             raise ValueError(f"a decode step takes at most 8 new tokens per row, got {seq_len}")
@@ -198,12 +230,12 @@ class TransformerLayer(Module):
 
     def __init__(self, n_embd: int, n_head: int, p_dropout: float = 0.1, ln_eps: float = 1e-8,
                  bias: bool = True, backend=None, use_fused_kernel: bool = False,
-                 use_flash_attention: bool = False, causal: bool = True):
+                 use_flash_attention: bool = False, causal: bool = True, n_kv_head=None):
         super().__init__()
         self.attention = MultiHeadAttention(n_embd, n_head, causal=causal, p_dropout=p_dropout,
                                             bias=bias, backend=backend,
                                             use_fused_kernel=use_fused_kernel,
-                                            use_flash_attention=use_flash_attention)
+                                            use_flash_attention=use_flash_attention, n_kv_head=n_kv_head)
         self.ff = FeedForward(n_embd, 256, p_dropout, bias, backend)
         self.use_fused_kernel = use_fused_kernel
         if use_fused_kernel:
@@ -232,7 +264,8 @@ class DecoderLM(Module):
 
     def __init__(self, n_vocab: int, n_embd: int, n_head: int, n_positions: int,
                  p_dropout: float = 0.1, ln_eps: float = 1e-5, bias: bool = True, backend=None,
-                 use_fused_kernel: bool = False, use_flash_attention: bool = False, n_layer: int = 4):
+                 use_fused_kernel: bool = False, use_flash_attention: bool = False, n_layer: int = 4,
+                 n_kv_head=None):
         super().__init__()
         self.backend = backend
         self.n_embd = n_embd
@@ -243,13 +276,15 @@ class DecoderLM(Module):
         for i in range(n_layer):
             setattr(self, f"t_layer_{i + 1}", TransformerLayer(
                 n_embd, n_head, p_dropout, ln_eps, bias, backend,
-                use_fused_kernel=use_fused_kernel, use_flash_attention=use_flash_attention))
+                use_fused_kernel=use_fused_kernel, use_flash_attention=use_flash_attention,
+                n_kv_head=n_kv_head))
         self.dropout = Dropout(p_dropout)
         self.lm_head = Linear(n_embd, n_vocab, bias, backend)
         self.use_fused_kernel = use_fused_kernel
         self.use_flash_attention = use_flash_attention
         self.n_positions = n_positions
         self.n_head = n_head
+        self.n_kv_head = n_head if n_kv_head is None else n_kv_head
         self.ln = FusedLayerNorm(n_embd, backend) if use_fused_kernel else LayerNorm1d(n_embd, ln_eps, backend)
         self.graph_captures = 0  # hipGraph captures of the decode step (generate(graph=True))
 
@@ -276,7 +311,7 @@ class DecoderLM(Module):
         """A KVCache for this model and a batch of batch_size rows."""
         from .kv_cache import KVCache
         return KVCache(self.n_layer, batch_size, self.n_head, self.n_positions, self.n_embd // self.n_head,
-                       self.backend)
+                       self.backend, n_kv_head=self.n_kv_head)
 
     def _forward_cached(self, idx, kv_len, cache):
         if not self.use_flash_attention:

@@ -353,8 +353,9 @@ class Tensor:
 
     def flash_attention_decode(self, Kc: "Tensor", Vc: "Tensor", kv_len=None, causal: bool = True) -> "Tensor":  # noqa: N803
         """Generation: self holds the Nq <= 8 newest query rows [B,H,Nq,d], Kc / Vc the key /
-        value caches [B,H,Nmax,d] whose first kv_len[b] rows are visible (a device count vector;
-        the queries are the last Nq of those positions). Inference only: the result has no history."""
+        value caches [B,Hkv,Nmax,d] whose first kv_len[b] rows are visible (a device count vector;
+        the queries are the last Nq of those positions). Hkv divides H (grouped-query attention:
+        query head h reads kv head h // (H // Hkv)). Inference only: the result has no history."""
         fn = self.backend.flash_attention_decode
         if fn is None:
             raise NotImplementedError("this backend has no decode attention kernel")

@@ -25,6 +25,17 @@ End to end: DecoderLM.generate tokens/s at config-5 width (V = 10000, E = 256, 8
                 that end in a device-to-host copy; the legs alternate inside every round
   select_token  mt_select_token alone at (B, V) = (8, 10000) and (64, 10000): greedy, top_k = 50
                 and the whole vocabulary at T = 1, device events around 64 launches, alternated
+
+--gqa-legs instead writes profiles/decode_gqa_bench.json: per large shape and Hkv in {H, H/4, H/8},
+alternated in one process like the legs above:
+
+  gqa       one mt_flash_attn_decode_gqa step at Nq = 1: H query heads, caches of Hkv heads
+            ([B, L, Hkv, d] storage)
+  repeated  mt_flash_attn_decode on K / V of H heads (what the same model costs with its K / V
+            repeated per group: H / Hkv times the bytes, the same arithmetic)
+  copy      a device-to-device copy of the gqa leg's own K and V bytes
+
+Each leg rotates over enough cache copies of its own to exceed twice the Infinity Cache.
 """
 import argparse
 import json
@@ -110,6 +121,100 @@ def bench_shape(torch, _hip, B, H, L, d, name, rounds, warmup):
         "decode_vs_copy_read_rate": (alg_bytes / med["decode"]) / (kv_bytes / med["copy"]),
         "full_over_decode": med["full"] / med["decode"],
     }
+
+
+def bench_gqa(torch, _hip, B, H, L, d, name, rounds, warmup):
+    dt = torch.bfloat16 if name == "bf16" else torch.float32
+    es = 2 if name == "bf16" else 4
+    code = 1 if name == "bf16" else 0
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rnd = lambda *s: torch.randn(*s, generator=g, device="cuda", dtype=torch.float32).to(dt)  # noqa: E731
+
+    def make_caches(heads):
+        kv_bytes = 2 * B * heads * L * d * es
+        nset = min(72, max(2, -(-2 * ICACHE // kv_bytes) + 1))
+        return kv_bytes, nset, [(rnd(B, L, heads, d).permute(0, 2, 1, 3), rnd(B, L, heads, d).permute(0, 2, 1, 3))
+                                for _ in range(nset)]
+    q = rnd(B, 1, H, d).permute(0, 2, 1, 3)
+    kvl = torch.full((B,), L, dtype=torch.int32, device="cuda")
+    o = torch.empty((B, 1, H, d), dtype=dt, device="cuda").permute(0, 2, 1, 3)
+    m, l = (torch.empty((B, H, 1), dtype=torch.float32, device="cuda") for _ in range(2))
+    rep_bytes, rep_nset, rep_caches = make_caches(H)
+    rep_ws_bytes = _hip.decode_workspace_bytes(code, B, H, 1, L, d)
+    rep_ws = torch.empty(max(1, rep_ws_bytes // 4), dtype=torch.float32, device="cuda")
+    rows = []
+    for Hkv in (H, H // 4, H // 8):
+        kv_bytes, nset, caches = (rep_bytes, rep_nset, rep_caches) if Hkv == H else make_caches(Hkv)
+        dst = (torch.empty_like(caches[0][0]), torch.empty_like(caches[0][1]))
+        nsplit, span, tile = _hip.decode_splits(code, B, H, 1, L, d, Hkv=Hkv)
+        ws_bytes = _hip.decode_workspace_bytes(code, B, H, 1, L, d, Hkv=Hkv)
+        ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device="cuda")
+
+        def gqa(i):
+            kc, vc = caches[i % nset]
+            _hip.flash_decode(q, kc, vc, kv_len=kvl, causal=True, out=o, m=m, l=l, workspace=ws)
+
+        def repeated(i):
+            kc, vc = rep_caches[i % rep_nset]
+            _hip.flash_decode(q, kc, vc, kv_len=kvl, causal=True, out=o, m=m, l=l, workspace=rep_ws)
+
+        def copy(i):
+            kc, vc = caches[i % nset]
+            dst[0].copy_(kc)
+            dst[1].copy_(vc)
+        # the two decode legs take as many launches per timing, whole turns over their cache sets
+        calls = 2 * nset * rep_nset
+        legs = {"gqa": (gqa, calls), "repeated": (repeated, calls), "copy": (copy, nset)}
+        for fn, inner in legs.values():
+            for _ in range(warmup):
+                _timed(torch, fn, inner)
+        times = {k: [] for k in legs}
+        for r in range(rounds):  # the legs alternate inside every round, the decode legs swapping places
+            order = ("gqa", "repeated", "copy") if r % 2 == 0 else ("repeated", "gqa", "copy")
+            for k in order:
+                fn, inner = legs[k]
+                times[k].append(_timed(torch, fn, inner))
+        med = {k: statistics.median(v) for k, v in times.items()}
+        alg_bytes = kv_bytes + 2 * B * H * d * es + 2 * ws_bytes
+        rep_alg_bytes = rep_bytes + 2 * B * H * d * es + 2 * rep_ws_bytes
+        G = H // Hkv
+        gs = min(G, 8)
+        rows.append({
+            "shape": [B, H, L, d], "dtype": name, "nq": 1, "kv_heads": Hkv, "group": G, "heads_per_workgroup": gs,
+            "workgroups_per_split": B * Hkv * -(-G // gs), "splits": nsplit, "span_keys": span, "tile_keys": tile,
+            "workspace_bytes": ws_bytes, "kv_bytes": kv_bytes, "gqa_algorithmic_bytes": alg_bytes,
+            "repeated_kv_bytes": rep_bytes, "repeated_algorithmic_bytes": rep_alg_bytes,
+            "cache_sets_rotated": nset, "repeated_cache_sets_rotated": rep_nset, "rounds": rounds,
+            "decode_launches_per_timing": calls,
+            "gqa_s_median": med["gqa"], "gqa_s_min": min(times["gqa"]),
+            "repeated_s_median": med["repeated"], "repeated_s_min": min(times["repeated"]),
+            "copy_s_median": med["copy"], "copy_s_min": min(times["copy"]),
+            "gqa_bytes_per_s": alg_bytes / med["gqa"],
+            "repeated_bytes_per_s": rep_alg_bytes / med["repeated"],
+            "copy_read_bytes_per_s": kv_bytes / med["copy"],
+            "gqa_over_repeated_time": med["gqa"] / med["repeated"],
+            # the one condition: fewer bytes, the same arithmetic -> not slower beyond the 4 % box-to-box variation
+            "gqa_not_slower_than_repeated": bool(med["gqa"] <= 1.04 * med["repeated"]),
+        })
+        print(json.dumps(rows[-1]), flush=True)
+        if Hkv != H:
+            del caches, dst
+            torch.cuda.empty_cache()
+    return rows
+
+
+def gqa_legs(args, torch, _hip):
+    res = {"device": torch.cuda.get_device_name(0), "kernels": []}
+    for B, H, L, d, name in SHAPES[:3]:
+        res["kernels"] += bench_gqa(torch, _hip, B, H, L, d, name, args.rounds, args.warmup)
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(args.gqa_out), exist_ok=True)
+    with open(args.gqa_out, "w") as f:
+        json.dump(res, f, indent=1)
+    slower = [(r["shape"], r["dtype"], r["kv_heads"]) for r in res["kernels"]
+              if r["group"] > 1 and not r["gqa_not_slower_than_repeated"]]
+    if slower:
+        raise SystemExit(f"the GQA step is slower than the repeated-K/V step at {slower}")
 
 
 def bench_generate(minitorch, n_positions, prompt_len, new_tokens, batch, rounds):
@@ -212,6 +317,9 @@ def main():
     ap.add_argument("--graph-legs", action="store_true",
                     help="run the generate(graph=True) and select_token legs instead, into --graph-out")
     ap.add_argument("--graph-out", default=os.path.join(ROOT, "profiles", "generate_graph_bench.json"))
+    ap.add_argument("--gqa-legs", action="store_true",
+                    help="run the grouped-query decode legs instead, into --gqa-out")
+    ap.add_argument("--gqa-out", default=os.path.join(ROOT, "profiles", "decode_gqa_bench.json"))
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--skip-generate", action="store_true")
@@ -223,6 +331,8 @@ def main():
     from minitorch import _hip
     if args.graph_legs:
         return graph_legs(args, torch, minitorch, _hip)
+    if args.gqa_legs:
+        return gqa_legs(args, torch, _hip)
     res = {"device": torch.cuda.get_device_name(0), "kernels": [], "generate": []}
     for B, H, L, d, name in SHAPES:
         r = bench_shape(torch, _hip, B, H, L, d, name, args.rounds, args.warmup)
