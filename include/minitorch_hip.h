@@ -285,6 +285,18 @@ int mt_matmul_f32(float* c, const float* a, const float* b, int64_t batch, int64
  * Every backend propagates ±inf and NaN operands as an IEEE fp32 product does (backends 2 and
  * 3 stage a non-finite value as its own piece; inf times a finite |b| < 2^-126 is NaN there). */
 void mt_set_gemm_backend(int backend);
+/* The kernel mt_matmul_f32 launches for this problem under `backend` (0..3 as above), decided by
+ * the function mt_matmul_f32 itself dispatches through: 0 rocBLAS, 1 rocBLAS on the library's
+ * own K slices plus an ordered sum, 2 the fp32-MFMA kernel, 3 the three-piece bf16 GEMM on
+ * 64x64 tiles, 4 the same on 128x128 tiles; negative for bad arguments (mt_last_error).
+ * out (may be NULL) = {ak, bk, vec, S, ks}: S k-slices of ks each (S = 1: no split); kernels
+ * 3 and 4: ak / bk = the operand is read along k, vec = 16-byte loads; rocBLAS: ak / bk = op N
+ * on A / B, vec = -1; kernel 2: ak = bk = vec = -1. a, b and c are used for their alignment
+ * only, never dereferenced. No device call: the intended plan; a split whose scratch cannot be
+ * allocated at run time still runs unsplit (the 128x128 one as the 64x64 plan). */
+int mt_matmul_f32_plan(int backend, int64_t batch, int64_t M, int64_t N, int64_t K,
+                       const int64_t* a_strides, const int64_t* b_strides, const int64_t* c_strides,
+                       const void* a, const void* b, const void* c, int32_t out[5]);
 
 /* out[0..n) <- U[0,1) from a stateless counter-based hash of (seed, index). Replaces the
  * host draws of the reference's dropout paths (minitorch/nn.py dropout via

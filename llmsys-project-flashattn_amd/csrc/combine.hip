@@ -1497,11 +1497,25 @@ __global__ __launch_bounds__(256) void splitk_sum_kernel(float* __restrict__ c, 
 }
 }  // extern "C++"
 
-// Row-major C[M,N] = A[M,K]·B[K,N] as column-major Cᵀ = Bᵀ·Aᵀ. Returns false (caller
-// falls back) when a layout has no unit stride or a leading dimension rocBLAS rejects.
-static bool gemm_rocblas(float* c, const float* a, const float* b, int64_t batch, int64_t M,
-                         int64_t N, int64_t K, const int64_t* sa, const int64_t* sb,
-                         const int64_t* sc, hipStream_t st, rocblas_status* status) {
+// What mt_matmul_f32 launches (mt_matmul_f32_plan reports it): every dispatch decision of the
+// GEMM is taken here, from the sizes, the strides and the pointers' alignment alone, with no
+// device call; the launchers below only carry it out. What can fail at run time (the rocBLAS
+// handle, a split's scratch, the big kernel's shared-memory attribute) falls back there.
+enum { kGemmRocblas = 0, kGemmRocblasSplit = 1, kGemmF32 = 2, kGemmX3 = 3, kGemmX3Big = 4 };
+struct GemmPlan {
+  int kernel;  // kGemm*; -1: refused (batch > 65535 on an own kernel)
+  int ak, bk;  // X3: the operand is contiguous along k; rocBLAS: op N on A / B; else -1
+  int vec;     // X3: 16-B loads; else -1
+  int S;       // k slices (1: none)
+  int64_t ks;  // k per slice
+  int64_t sam, sak, sbk, sbn, scm;  // strides with those of size-1 dimensions normalised
+  int64_t lda, ldb;                 // rocBLAS leading dimensions
+};
+
+// Row-major C[M,N] = A[M,K]·B[K,N] as column-major Cᵀ = Bᵀ·Aᵀ on rocBLAS: false when a layout
+// has no unit stride or a leading dimension rocBLAS rejects.
+static bool gemm_plan_rocblas(GemmPlan& p, int64_t batch, int64_t M, int64_t N, int64_t K, const int64_t* sa,
+                              const int64_t* sb, const int64_t* sc, const void* c) {
   const int64_t lim = 0x7fffffff;
   if (M > lim || N > lim || K > lim || batch > lim) return false;
   // Normalise the strides of size-1 dims (free) towards a usable layout.
@@ -1511,22 +1525,19 @@ static bool gemm_rocblas(float* c, const float* a, const float* b, int64_t batch
   if (K == 1) { sak = 1; sbk = std::max<int64_t>(N, sbk); }
   if (sc[0] < 0 || scn != 1 || scm < N) return false;
   // first operand: our B as an N x K column-major matrix (op N) or its K x N transpose
-  rocblas_operation opb;
-  int64_t ldb;
-  if (sbn == 1 && sbk >= N) { opb = rocblas_operation_none; ldb = sbk; }
-  else if (sbk == 1 && sbn >= K) { opb = rocblas_operation_transpose; ldb = sbn; }
+  if (sbn == 1 && sbk >= N) { p.bk = 1; p.ldb = sbk; }
+  else if (sbk == 1 && sbn >= K) { p.bk = 0; p.ldb = sbn; }
   else return false;
   // second operand: our A as a K x M column-major matrix (op N) or its M x K transpose
-  rocblas_operation opa;
-  int64_t lda;
-  if (sak == 1 && sam >= K) { opa = rocblas_operation_none; lda = sam; }
-  else if (sam == 1 && sak >= M) { opa = rocblas_operation_transpose; lda = sak; }
+  if (sak == 1 && sam >= K) { p.ak = 1; p.lda = sam; }
+  else if (sam == 1 && sak >= M) { p.ak = 0; p.lda = sak; }
   else return false;
-  if (lda > lim || ldb > lim || scm > lim || sa[0] < 0 || sb[0] < 0) return false;
-  rocblas_handle h = blas_handle();
-  if (!h) return false;
-  rocblas_set_stream(h, st);
-  const float alpha = 1.f, beta = 0.f;
+  if (p.lda > lim || p.ldb > lim || scm > lim || sa[0] < 0 || sb[0] < 0) return false;
+  p.kernel = kGemmRocblas;
+  p.vec = -1;
+  p.S = 1;
+  p.ks = K;
+  p.sam = sam; p.sak = sak; p.sbk = sbk; p.sbn = sbn; p.scm = scm;
   // A long reduction into a small output (config 5's LM-head dX: 4992 x 256 over K = 10000,
   // 78 output tiles for 256 CUs) runs as S batched K slices into partials plus an ordered sum:
   // 547 -> 197 µs at S = 8; the linears' 256 x 256 dW over K = 4992 (rocBLAS's own split,
@@ -1535,12 +1546,119 @@ static bool gemm_rocblas(float* c, const float* a, const float* b, int64_t batch
   const int64_t tiles = ((M + 127) / 128) * ((N + 127) / 128);
   if (batch == 1 && ((K >= 8192 && tiles < 128) || (K >= 4096 && tiles <= 16)) && N % 4 == 0 && scm % 4 == 0 &&
       ((uintptr_t)c & 15) == 0) {
-    int S = 0;
     for (int cand : {8, 4, 2})
-      if (K % cand == 0 && K / cand >= 1024 && (K >= 8192 || cand <= 4)) { S = cand; break; }
-    float* part = S ? (float*)reduce_scratch((size_t)S * M * N * 4, st) : nullptr;
+      if (K % cand == 0 && K / cand >= 1024 && (K >= 8192 || cand <= 4)) {
+        p.kernel = kGemmRocblasSplit;
+        p.S = cand;
+        p.ks = K / cand;
+        break;
+      }
+  }
+  return true;
+}
+
+// The X3 GEMM: false when a layout has no unit stride. Split-K when one matrix has fewer than
+// 256 output tiles and K >= 512 (config 5's 256 x 256 weight gradients over K = 4992: 16 tiles
+// -> 16 slices). big: 128x128 tiles where they fill the chip (alone or as k-slices), else 64x64.
+static bool gemm_plan_x3(GemmPlan& p, bool big, int64_t batch, int64_t M, int64_t N, int64_t K, const int64_t* sa,
+                         const int64_t* sb, const void* a, const void* b) {
+  int64_t sam = sa[1], sak = sa[2], sbk = sb[1], sbn = sb[2];
+  if (K == 1) { sak = 1; sbk = 1; }
+  if (M == 1) sam = 1;
+  if (N == 1) sbn = 1;
+  const bool ak = sak == 1, bk = sbk == 1;
+  if ((!ak && sam != 1) || (!bk && sbn != 1)) return false;
+  if (batch > 65535) return false;
+  // 16-B chunks: the bases and every stride but the unit one multiples of 4 floats
+  const int64_t oa = ak ? sam : sak, ob = bk ? sbn : sbk;
+  const bool vec = (((uintptr_t)a | (uintptr_t)b) & 15) == 0 && oa % 4 == 0 && ob % 4 == 0 &&
+                   (batch == 1 || (sa[0] % 4 == 0 && sb[0] % 4 == 0));
+  p.ak = ak; p.bk = bk; p.vec = vec;
+  p.sam = sam; p.sak = sak; p.sbk = sbk; p.sbn = sbn;
+  const int64_t tm2 = (M + 127) / 128, tn2 = (N + 127) / 128;
+  // 128x128 tiles where they fill the chip, alone or as up to 8 k-slices of >= 1024
+  int S2 = 1;
+  if (batch == 1 && tm2 * tn2 < 256) S2 = (int)std::min<int64_t>((256 + tm2 * tn2 - 1) / (tm2 * tn2), K / 1024);
+  int64_t ks2 = K;
+  if (S2 > 8) S2 = 1;
+  if (S2 > 1) {
+    ks2 = ((K + S2 - 1) / S2 + 15) / 16 * 16;
+    S2 = (int)((K + ks2 - 1) / ks2);
+  }
+  if (big && batch * tm2 * tn2 * S2 >= 256 && tm2 <= 65535) {
+    p.kernel = kGemmX3Big;
+    p.S = S2;
+    p.ks = ks2;
+    return true;
+  }
+  const int64_t tm = (M + 63) / 64, tn = (N + 63) / 64;
+  if (tm > 65535) return false;
+  int S = 1;
+  if (batch == 1 && tm * tn < 256 && K >= 512) {
+    S = (int)std::min<int64_t>(16, std::max<int64_t>(1, 256 / (tm * tn)));
+    S = (int)std::min<int64_t>(S, K / 256);
+  }
+  int64_t ks = K;
+  if (S > 1) {
+    ks = ((K + S - 1) / S + 31) / 32 * 32;
+    S = (int)((K + ks - 1) / ks);
+    if (S <= 1) { S = 1; ks = K; }
+  }
+  p.kernel = kGemmX3;
+  p.S = S;
+  p.ks = ks;
+  return true;
+}
+
+// backend: 0..3 as mt_set_gemm_backend (any other value: the fp32 kernel, as 1)
+static GemmPlan gemm_plan(int backend, int64_t batch, int64_t M, int64_t N, int64_t K, const int64_t* sa,
+                          const int64_t* sb, const int64_t* sc, const void* a, const void* b, const void* c) {
+  GemmPlan p;
+  memset(&p, 0, sizeof(p));
+  if ((backend == 2 || backend == 3) && gemm_plan_x3(p, backend == 2, batch, M, N, K, sa, sb, a, b)) return p;
+  if (backend == 0 && gemm_plan_rocblas(p, batch, M, N, K, sa, sb, sc, c)) return p;
+  p.kernel = batch > 65535 ? -1 : kGemmF32;
+  p.ak = p.bk = p.vec = -1;
+  p.S = 1;
+  p.ks = K;
+  return p;
+}
+
+int mt_matmul_f32_plan(int backend, int64_t batch, int64_t M, int64_t N, int64_t K, const int64_t* a_strides,
+                       const int64_t* b_strides, const int64_t* c_strides, const void* a, const void* b,
+                       const void* c, int32_t out[5]) {
+  if (backend < 0 || backend > 3) return set_error("mt_matmul_f32_plan: backend %d not in 0..3", backend), -1;
+  if (batch <= 0 || M <= 0 || N <= 0 || K <= 0)
+    return set_error("mt_matmul_f32_plan: bad sizes %lld %lld %lld %lld", (long long)batch, (long long)M,
+                     (long long)N, (long long)K), -1;
+  if (!a_strides || !b_strides || !c_strides) return set_error("mt_matmul_f32_plan: strides are NULL"), -1;
+  const GemmPlan p = gemm_plan(backend, batch, M, N, K, a_strides, b_strides, c_strides, a, b, c);
+  if (p.kernel < 0) return set_error("mt_matmul_f32_plan: batch %lld > 65535", (long long)batch), -1;
+  if (out) {
+    out[0] = p.ak; out[1] = p.bk; out[2] = p.vec; out[3] = p.S;
+    out[4] = (int32_t)std::min<int64_t>(p.ks, 0x7fffffff);
+  }
+  return p.kernel;
+}
+
+// The rocBLAS plans (kGemmRocblas, kGemmRocblasSplit). Returns false (caller falls back) when
+// there is no rocBLAS handle.
+static bool gemm_rocblas(const GemmPlan& p, float* c, const float* a, const float* b, int64_t batch, int64_t M,
+                         int64_t N, int64_t K, const int64_t* sa, const int64_t* sb,
+                         const int64_t* sc, hipStream_t st, rocblas_status* status) {
+  const rocblas_operation opb = p.bk ? rocblas_operation_none : rocblas_operation_transpose;
+  const rocblas_operation opa = p.ak ? rocblas_operation_none : rocblas_operation_transpose;
+  const int64_t lda = p.lda, ldb = p.ldb, scm = p.scm;
+  rocblas_handle h = blas_handle();
+  if (!h) return false;
+  rocblas_set_stream(h, st);
+  const float alpha = 1.f, beta = 0.f;
+  if (p.kernel == kGemmRocblasSplit) {
+    const int S = p.S;
+    // without scratch: one unsplit call
+    float* part = (float*)reduce_scratch((size_t)S * M * N * 4, st);
     if (part) {
-      const int64_t ks = K / S;
+      const int64_t ks = p.ks;
       // slice s: B rows [s ks, (s+1) ks) (the first operand's K offset), A columns likewise
       const int64_t strb = opb == rocblas_operation_none ? ks * ldb : ks;
       const int64_t stra = opa == rocblas_operation_none ? ks : ks * lda;
@@ -1562,37 +1680,22 @@ static bool gemm_rocblas(float* c, const float* a, const float* b, int64_t batch
   return true;
 }
 
-// The X3 GEMM (gemm_x3_kernel): false when a layout has no unit stride (the caller falls back).
-// Split-K when one matrix has fewer than 256 output tiles and K >= 512 (config 5's 256 x 256
-// weight gradients over K = 4992: 16 tiles -> 16 slices).
-// big: 128x128 tiles where they fill the chip (alone or as k-slices), else 64x64.
-static bool gemm_x3(float* c, const float* a, const float* b, int64_t batch, int64_t M, int64_t N,
-                    int64_t K, const int64_t* sa, const int64_t* sb, const int64_t* sc, hipStream_t st,
-                    bool big) {
-  int64_t sam = sa[1], sak = sa[2], sbk = sb[1], sbn = sb[2];
-  if (K == 1) { sak = 1; sbk = 1; }
-  if (M == 1) sam = 1;
-  if (N == 1) sbn = 1;
-  const bool ak = sak == 1, bk = sbk == 1;
-  if ((!ak && sam != 1) || (!bk && sbn != 1)) return false;
-  if (batch > 65535) return false;
-  // 16-B chunks: the bases and every stride but the unit one multiples of 4 floats
-  const int64_t oa = ak ? sam : sak, ob = bk ? sbn : sbk;
-  const bool vec = (((uintptr_t)a | (uintptr_t)b) & 15) == 0 && oa % 4 == 0 && ob % 4 == 0 &&
-                   (batch == 1 || (sa[0] % 4 == 0 && sb[0] % 4 == 0));
-  const int64_t tm2 = (M + 127) / 128, tn2 = (N + 127) / 128;
-  // 128x128 tiles where they fill the chip, alone or as up to 8 k-slices of >= 1024
-  int S2 = 1;
-  if (batch == 1 && tm2 * tn2 < 256) S2 = (int)std::min<int64_t>((256 + tm2 * tn2 - 1) / (tm2 * tn2), K / 1024);
-  int64_t ks2 = K;
-  if (S2 > 8) S2 = 1;
-  if (S2 > 1) {
-    ks2 = ((K + S2 - 1) / S2 + 15) / 16 * 16;
-    S2 = (int)((K + ks2 - 1) / ks2);
-  }
+// The X3 plans (kGemmX3Big, kGemmX3). Without scratch for its slices the big plan runs as the
+// 64x64 plan of the same problem, and that one unsplit. false (the caller falls back to the fp32
+// kernel) when the big kernel's shared memory cannot be set.
+static bool gemm_x3(GemmPlan p, float* c, const float* a, const float* b, int64_t batch, int64_t M, int64_t N,
+                    int64_t K, const int64_t* sa, const int64_t* sb, const int64_t* sc, hipStream_t st) {
   float* part2 = nullptr;
-  if (big && batch * tm2 * tn2 * S2 >= 256 && tm2 <= 65535 &&
-      (S2 == 1 || (part2 = (float*)reduce_scratch((size_t)S2 * M * N * 4, st)) != nullptr)) {
+  if (p.kernel == kGemmX3Big && p.S > 1 &&
+      (part2 = (float*)reduce_scratch((size_t)p.S * M * N * 4, st)) == nullptr) {
+    p = gemm_plan(3, batch, M, N, K, sa, sb, sc, a, b, c);
+    if (p.kernel != kGemmX3) return false;
+  }
+  const int64_t sam = p.sam, sak = p.sak, sbk = p.sbk, sbn = p.sbn;
+  const bool ak = p.ak, bk = p.bk, vec = p.vec;
+  if (p.kernel == kGemmX3Big) {
+    const int S2 = p.S;
+    const int64_t ks2 = p.ks, tm2 = (M + 127) / 128, tn2 = (N + 127) / 128;
     GemmX3Args g;
     g.a = a; g.b = b; g.c = S2 > 1 ? part2 : c;
     g.M = M; g.N = N; g.K = K; g.ks = ks2; g.S = S2;
@@ -1626,18 +1729,11 @@ static bool gemm_x3(float* c, const float* a, const float* b, int64_t batch, int
     return true;
   }
   const int64_t tm = (M + 63) / 64, tn = (N + 63) / 64;
-  if (tm > 65535) return false;
-  int S = 1;
-  if (batch == 1 && tm * tn < 256 && K >= 512) {
-    S = (int)std::min<int64_t>(16, std::max<int64_t>(1, 256 / (tm * tn)));
-    S = (int)std::min<int64_t>(S, K / 256);
-  }
-  int64_t ks = K;
+  int S = p.S;
+  int64_t ks = p.ks;
   float* part = nullptr;
   if (S > 1) {
-    ks = ((K + S - 1) / S + 31) / 32 * 32;
-    S = (int)((K + ks - 1) / ks);
-    if (S > 1) part = (float*)reduce_scratch((size_t)S * M * N * 4, st);
+    part = (float*)reduce_scratch((size_t)S * M * N * 4, st);
     if (!part) { S = 1; ks = K; }
   }
   GemmX3Args g;
@@ -1669,13 +1765,13 @@ int mt_matmul_f32(float* c, const float* a, const float* b, int64_t batch, int64
   if (batch <= 0 || M <= 0 || N <= 0 || K <= 0)
     return set_error("mt_matmul_f32: bad sizes %lld %lld %lld %lld", (long long)batch,
                      (long long)M, (long long)N, (long long)K);
-  if ((g_gemm_backend == 2 || g_gemm_backend == 3) &&
-      gemm_x3(c, a, b, batch, M, N, K, a_strides, b_strides, c_strides, (hipStream_t)stream,
-              g_gemm_backend == 2))
+  const GemmPlan p = gemm_plan(g_gemm_backend, batch, M, N, K, a_strides, b_strides, c_strides, a, b, c);
+  if ((p.kernel == kGemmX3 || p.kernel == kGemmX3Big) &&
+      gemm_x3(p, c, a, b, batch, M, N, K, a_strides, b_strides, c_strides, (hipStream_t)stream))
     return check_hip(hipGetLastError(), "mt_matmul_f32(x3)");
-  if (g_gemm_backend == 0) {
+  if (p.kernel == kGemmRocblas || p.kernel == kGemmRocblasSplit) {
     rocblas_status rs = rocblas_status_success;
-    if (gemm_rocblas(c, a, b, batch, M, N, K, a_strides, b_strides, c_strides, (hipStream_t)stream, &rs)) {
+    if (gemm_rocblas(p, c, a, b, batch, M, N, K, a_strides, b_strides, c_strides, (hipStream_t)stream, &rs)) {
       if (rs != rocblas_status_success)
         return set_error("mt_matmul_f32: rocblas_sgemm_strided_batched: %s", rocblas_status_to_string(rs));
       return check_hip(hipGetLastError(), "mt_matmul_f32(rocblas)");

@@ -89,6 +89,8 @@ _PROTOS = {
     "mt_adam_step_dstep": (_int, [_int, _vpp, _vpp, _vpp, _vpp, _i64p, ctypes.c_double, ctypes.c_double,
                                   ctypes.c_double, _vp, _vp]),
     "mt_set_gemm_backend": (None, [_int]),
+    "mt_matmul_f32_plan": (_int, [_int, _i64, _i64, _i64, _i64, _i64p, _i64p, _i64p, _vp, _vp, _vp,
+                                  ctypes.POINTER(ctypes.c_int32)]),
     "launch_attn_softmax": (None, [_fp, _fp, _int, _int, _int, _int, ctypes.c_bool, _vp]),
     "launch_attn_softmax_bw": (None, [_fp, _fp, _int, _int, _vp]),
     "launch_layernorm": (None, [_fp] * 6 + [_int, _int, _vp]),
@@ -477,6 +479,21 @@ def scratch_bytes() -> int:
 def scratch_release() -> None:
     """Free the library's stream scratch that no captured graph holds (mt_scratch_release)."""
     check(lib().mt_scratch_release(), "mt_scratch_release")
+
+
+def matmul_plan(backend: int, batch: int, M: int, N: int, K: int, a_strides, b_strides, c_strides,
+                a_ptr: int = 0, b_ptr: int = 0, c_ptr: int = 0):
+    """(kernel, ak, bk, vec, S, ks) of mt_matmul_f32 for this problem under GEMM backend `backend`
+    (mt_matmul_f32_plan: kernel 0 rocBLAS, 1 rocBLAS on own K slices, 2 the fp32-MFMA kernel,
+    3 / 4 the X3 GEMM on 64x64 / 128x128 tiles). Strides are (batch, row, col) triples in
+    elements; the pointers count for their alignment only. No device call."""
+    out = (ctypes.c_int32 * 5)()
+    s3 = lambda s: (ctypes.c_int64 * 3)(*[int(x) for x in s])  # noqa: E731
+    kern = lib().mt_matmul_f32_plan(backend, batch, M, N, K, s3(a_strides), s3(b_strides), s3(c_strides),
+                                    a_ptr or None, b_ptr or None, c_ptr or None, out)
+    if kern < 0:
+        raise ValueError(lib().mt_last_error().decode(errors="replace"))
+    return (kern, *out)
 
 
 def exported_symbols() -> Sequence[str]:
