@@ -162,6 +162,42 @@ int mt_flash_attn_decode_gqa(int dtype, int causal, const void* q, const void* k
                              int64_t Nk, int64_t d, const int64_t* q_strides, const int64_t* k_strides,
                              const int64_t* v_strides, const int64_t* o_strides, const int* kv_len,
                              void* workspace, int64_t workspace_bytes, void* stream);
+/* Extend step: Nq >= 1 new query rows per (batch, head) at the END of a row of cached keys, of
+ * which t = clamp(q_len[b], 0, Nq) are real (q_len: device int32 [B]; NULL = Nq; the batch is
+ * right-padded). n = clamp(kv_len[b], 0, Nk) is the number of keys row b holds AFTER its new
+ * rows were appended (kv_len: device int32 [B]; NULL = Nk). Query i < t sits at position
+ * n - t + i: with causal != 0 it sees the keys j < clamp(n - t + 1 + i, 0, n) (the causal mask
+ * aligned bottom-right), else every key j < n. A query i >= t, or one with no visible key, gets
+ * O = 0, m = -inf, l = 0 exactly. With q_len = NULL and Nq <= 8 this is
+ * mt_flash_attn_decode_gqa's contract.
+ *   q, o:              [B, H, Nq, d], strides (batch, head, row) in elements, NULL = contiguous
+ *   k_cache, v_cache:  [B, Hkv, Nk, d] likewise; query head h reads kv head h / (H / Hkv)
+ *   m, l:              fp32 [B*H*Nq] or NULL; m + log(l) is the row's log-sum-exp
+ * Cache rows j >= n and Q rows i >= t are never read (the cache tail may be uninitialised
+ * memory): their loads are predicated on the row and the logits replaced by -inf through a
+ * select, so no product is formed with such a row's data.
+ * dtype: MT_F32, MT_BF16, or MT_BF16_F32OUT (bf16 Q/K/V, fp32 O). fp32 with d <= 64 runs both
+ * products on the bf16 MFMA with three bf16 pieces per operand (fp32 accuracy), fp32 above that
+ * on the fp32 MFMA. Requires 1 <= Nq <= Nk, d <= 256 and 16-B rows as decode defines them: d,
+ * every stride and every base pointer a multiple of 16 bytes.
+ * Refused with a status and a mt_last_error() message before any device call: whatever
+ * mt_flash_attn_decode_gqa refuses (but for Nq > 8), Nq > Nk, Hkv <= 0, Hkv > H, H % Hkv != 0.
+ * One launch on the caller's stream: no workspace, no allocation, no synchronisation, plain
+ * stores only. The launch (grid and kernel) is a function of the sizes alone, never of kv_len
+ * or q_len, which only set loop bounds read on the device: a captured launch can be replayed
+ * as the cache fills. A workgroup owns block_queries query rows of one (b, h) and streams the
+ * keys in tiles of tile_keys; a workgroup whose queries are all >= t loads nothing.
+ * mt_flash_attn_extend_plan: the kernel id (>= 0) mt_flash_attn_extend launches at these sizes
+ * (the launcher dispatches through the same function), or a negative value with a message; it
+ * writes the query rows per workgroup and the keys per inner tile (either may be NULL) and
+ * makes no device call. */
+int mt_flash_attn_extend_plan(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk,
+                              int64_t d, int64_t* block_queries, int64_t* tile_keys);
+int mt_flash_attn_extend(int dtype, int causal, const void* q, const void* k_cache, const void* v_cache,
+                         void* o, float* m, float* l, int64_t B, int64_t H, int64_t Hkv, int64_t Nq,
+                         int64_t Nk, int64_t d, const int64_t* q_strides, const int64_t* k_strides,
+                         const int64_t* v_strides, const int64_t* o_strides,
+                         const int* kv_len, const int* q_len, void* stream);
 /* Copies the Nq new K and V rows of every (b, h) ([B, H, Nq, d]) into the caches
  * ([B, H, Nmax, d]) at rows pos[b] .. pos[b] + Nq - 1 (pos: device int32 [B]); rows outside
  * [0, Nmax) are dropped and nothing else in the caches is written. 16-B rows as above. */

@@ -1,9 +1,11 @@
 // C ABI of the KV-cache decode path (include/minitorch_hip.h): mt_flash_attn_decode[_gqa] and
-// their split / workspace queries, mt_kv_cache_append. The plain entry points are the Hkv = H
-// case of the grouped-query ones. Kernels: fa_decode.hip. Every argument is
+// their split / workspace queries, mt_kv_cache_append, and the extend step mt_flash_attn_extend
+// with its plan query. The plain entry points are the Hkv = H
+// case of the grouped-query ones. Kernels: fa_decode.hip, fa_extend.hip. Every argument is
 // validated before the first device call, as the other mt_flash_attn_* entry points do.
 #include "../../include/minitorch_hip.h"
 #include "fa_decode.h"
+#include "fa_extend.h"
 #include <math.h>
 
 namespace mt {
@@ -24,6 +26,29 @@ static int decode_sizes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq
   const int epc = dtype == MT_F32 ? 4 : 8;
   if (d % epc)
     return set_error("decode needs 16-B rows: d=%lld is not a multiple of %d", (long long)d, epc);
+  return 0;
+}
+
+// the extend step's sizes: decode's rules with 1 <= Nq <= Nk in place of Nq <= 8
+static int extend_sizes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d) {
+  if (dtype != MT_F32 && dtype != MT_BF16 && dtype != MT_BF16_F32OUT)
+    return set_error("unsupported dtype %d", dtype);
+  if (B <= 0 || H <= 0 || Nk <= 0 || d <= 0)
+    return set_error("bad sizes B=%lld H=%lld Nk=%lld d=%lld", (long long)B, (long long)H,
+                     (long long)Nk, (long long)d);
+  if (Hkv <= 0 || Hkv > H || H % Hkv)
+    return set_error("kv heads must divide the query heads (H=%lld, Hkv=%lld)", (long long)H, (long long)Hkv);
+  if (Nq < 1) return set_error("extend takes at least one query row per head (Nq=%lld)", (long long)Nq);
+  if (Nq > Nk)
+    return set_error("extend takes at most Nk query rows per head (Nq=%lld > Nk=%lld)", (long long)Nq,
+                     (long long)Nk);
+  if (d > 256) return set_error("extend head dim out of range (d=%lld; d <= 256)", (long long)d);
+  // the flat grid holds ceil(Nq / 128) * B * H workgroups, twice that for fp32 d > 128
+  if (Nk > (1 << 30) || B * H * Nq > (1ll << 31) - 1 || B * H * ((Nq + 127) / 128) > (1ll << 30) - 1)
+    return set_error("sizes out of range (Nk=%lld, B*H*Nq=%lld)", (long long)Nk, (long long)(B * H * Nq));
+  const int epc = dtype == MT_F32 ? 4 : 8;
+  if (d % epc)
+    return set_error("extend needs 16-B rows: d=%lld is not a multiple of %d", (long long)d, epc);
   return 0;
 }
 
@@ -115,6 +140,39 @@ int mt_flash_attn_decode(int dtype, int causal, const void* q, const void* k_cac
                          void* workspace, int64_t workspace_bytes, void* stream) {
   return mt_flash_attn_decode_gqa(dtype, causal, q, k_cache, v_cache, o, m, l, B, H, H, Nq, Nk, d, q_strides,
                                   k_strides, v_strides, o_strides, kv_len, workspace, workspace_bytes, stream);
+}
+
+int mt_flash_attn_extend_plan(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d,
+                              int64_t* block_queries, int64_t* tile_keys) {
+  if (extend_sizes(dtype, B, H, Hkv, Nq, Nk, d)) return -1;
+  const ExtendPlan p = extend_plan(dtype == MT_F32 ? 4 : 2, d);
+  if (block_queries) *block_queries = p.bq;
+  if (tile_keys) *tile_keys = p.bk;
+  return p.kernel;
+}
+
+int mt_flash_attn_extend(int dtype, int causal, const void* q, const void* k_cache, const void* v_cache,
+                         void* o, float* m, float* l, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk,
+                         int64_t d, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                         const int64_t* o_strides, const int* kv_len, const int* q_len, void* stream) {
+  if (int rc = extend_sizes(dtype, B, H, Hkv, Nq, Nk, d)) return rc;
+  const int esize = dtype == MT_F32 ? 4 : 2, osize = dtype == MT_BF16 ? 2 : 4;
+  ExtendArgs a;
+  a.q = q; a.k = k_cache; a.v = v_cache; a.o = o; a.m = m; a.l = l;
+  a.kv_len = kv_len; a.q_len = q_len;
+  strides_or_dense(a.qs, q_strides, H, Nq, d);
+  strides_or_dense(a.ks, k_strides, Hkv, Nk, d);
+  strides_or_dense(a.vs, v_strides, Hkv, Nk, d);
+  strides_or_dense(a.os, o_strides, H, Nq, d);
+  if (int rc = aligned16("q", q, a.qs, esize)) return rc;
+  if (int rc = aligned16("k_cache", k_cache, a.ks, esize)) return rc;
+  if (int rc = aligned16("v_cache", v_cache, a.vs, esize)) return rc;
+  if (int rc = aligned16("o", o, a.os, osize)) return rc;
+  a.H = (int)H; a.Hkv = (int)Hkv; a.Nq = (int)Nq; a.Nk = (int)Nk; a.d = (int)d;
+  a.nqb = (int)((Nq + extend_plan(esize, d).bq - 1) / extend_plan(esize, d).bq);
+  a.causal = causal != 0; a.o_f32 = osize == 4;
+  a.scale_log2 = (float)(1.4426950408889634 / sqrt((double)d));
+  return check_hip(launch_extend(a, esize == 2, B, (hipStream_t)stream), "mt_flash_attn_extend");
 }
 
 int mt_kv_cache_append(int dtype, const void* k_new, const void* v_new, void* k_cache, void* v_cache,

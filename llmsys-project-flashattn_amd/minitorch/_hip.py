@@ -60,6 +60,9 @@ _PROTOS = {
     "mt_flash_attn_decode_gqa_workspace_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64, _i64]),
     "mt_flash_attn_decode_gqa": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
                                         _i64p, _i64p, _i64p, _i64p, _vp, _vp, _i64, _vp]),
+    "mt_flash_attn_extend_plan": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64p, _i64p]),
+    "mt_flash_attn_extend": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
+                                    _i64p, _i64p, _i64p, _i64p, _vp, _vp, _vp]),
     "mt_kv_cache_append": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                   _i64p, _i64p, _i64p, _i64p, _vp, _vp]),
     "mt_select_token": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _i64, ctypes.c_uint64, _vp, _i64,
@@ -388,6 +391,54 @@ def flash_decode(q, k_cache, v_cache, kv_len=None, causal: bool = True, out=None
         None if workspace is None else workspace.data_ptr(),
         0 if workspace is None else workspace.numel() * workspace.element_size(), st),
         "mt_flash_attn_decode_gqa")
+    return out, m, l
+
+
+def extend_plan(dtype: int, B: int, H: int, Nq: int, Nk: int, d: int, Hkv: Optional[int] = None):
+    """(kernel id, block_queries, tile_keys) of mt_flash_attn_extend at these sizes (dtype: an MT_*
+    code): the instantiation it launches, the query rows one workgroup owns and the keys of one
+    inner tile. A function of the sizes only; no device call. Hkv: the caches' heads (None: H)."""
+    bq, bk = ctypes.c_int64(0), ctypes.c_int64(0)
+    kid = lib().mt_flash_attn_extend_plan(dtype, B, H, H if Hkv is None else Hkv, Nq, Nk, d,
+                                          ctypes.byref(bq), ctypes.byref(bk))
+    if kid < 0:
+        raise ValueError(lib().mt_last_error().decode(errors="replace"))
+    return kid, bq.value, bk.value
+
+
+def flash_extend(q, k_cache, v_cache, kv_len=None, q_len=None, causal: bool = True, out=None, m=None, l=None,
+                 out_dtype=None, stream: Optional[int] = None):
+    """Extend attention (mt_flash_attn_extend): q [B,H,Nq,d], any 1 <= Nq <= Nk new rows at the end
+    of each row, of which the first q_len[b] are real (None: all Nq; the batch is right-padded),
+    against the caches [B,Hkv,Nk,d] (any strides with unit-stride d; Hkv divides H), which hold
+    kv_len[b] rows after the new ones were appended (None: Nk). Query i < q_len[b] sits at position
+    kv_len[b] - q_len[b] + i. Returns (O, m, l); m, l fp32 [B,H,Nq]; a query >= q_len[b] or without
+    a visible key gets (0, -inf, 0). One launch, no workspace."""
+    torch = _torch()
+    _check_dev(q, k_cache, v_cache)
+    B, H, Nq, d = q.shape
+    Hkv, Nk = k_cache.shape[1], k_cache.shape[2]
+    if k_cache.shape != (B, Hkv, Nk, d) or v_cache.shape != k_cache.shape:
+        raise ValueError(f"cache shapes {tuple(k_cache.shape)} {tuple(v_cache.shape)} do not match q {tuple(q.shape)}")
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"the caches' {Hkv} heads do not divide q's {H} heads")
+    if not (q.dtype == k_cache.dtype == v_cache.dtype):
+        raise TypeError("q/k_cache/v_cache dtypes differ")
+    code = _decode_code(q, out, out_dtype)
+    if out is None:
+        out = torch.empty((B, H, Nq, d), dtype=torch.float32 if code == 2 else q.dtype, device=q.device)
+    if m is None:
+        m = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    if l is None:
+        l = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    kv = _kv_arg(kv_len, B, q.device)
+    ql = _kv_arg(q_len, B, q.device)
+    st = stream_ptr(q.device) if stream is None else stream
+    check(lib().mt_flash_attn_extend(
+        code, int(causal), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(),
+        m.data_ptr(), l.data_ptr(), B, H, Hkv, Nq, Nk, d, strides3(q), strides3(k_cache), strides3(v_cache),
+        strides3(out), None if kv is None else kv.data_ptr(), None if ql is None else ql.data_ptr(), st),
+        "mt_flash_attn_extend")
     return out, m, l
 
 

@@ -518,6 +518,23 @@ class HipKernelOps(TensorOps):
         return _wrap(o, (B, H, Nq, d), Q.backend, so)
 
     @staticmethod
+    def flash_attention_extend(Q: Tensor, Kc: Tensor, Vc: Tensor, kv_len=None, q_len=None,
+                               causal: bool = True) -> Tensor:
+        """O [B,H,Nq,d] of any 1 <= Nq <= Nmax new query rows, the first q_len[b] of them real,
+        against the caches Kc / Vc [B,Hkv,Nmax,d], which hold kv_len[b] rows with the new ones
+        (mt_flash_attn_extend). Rows >= q_len[b] of O are zero. Inference only. O is laid out
+        like Q's storage."""
+        import torch
+        B, H, Nq, d = Q.shape
+        so = _layout_like(Q)
+        o = torch.empty(B * H * Nq * d, dtype=torch.float32, device="cuda")
+        _hip.flash_extend(_torch_view(Q), _torch_view(Kc), _torch_view(Vc),
+                          kv_len=None if kv_len is None else HipKernelOps._i32(kv_len),
+                          q_len=None if q_len is None else HipKernelOps._i32(q_len), causal=causal,
+                          out=torch.as_strided(o, (B, H, Nq, d), so))
+        return _wrap(o, (B, H, Nq, d), Q.backend, so)
+
+    @staticmethod
     def kv_cache_append(Knew: Tensor, Vnew: Tensor, Kc: Tensor, Vc: Tensor, pos) -> None:
         """Write the new rows Knew / Vnew [B,Hkv,Nq,d] into the caches [B,Hkv,Nmax,d] at rows
         pos[b] .. (rows past the capacity are dropped)."""

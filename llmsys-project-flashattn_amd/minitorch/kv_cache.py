@@ -5,7 +5,9 @@ A decode step then needs the new tokens' Q/K/V and one read of each layer's cach
 holds K and V as ``[B, n_positions, Hkv, d]`` storage (the layout ``MultiHeadAttention`` projects
 into), seen by the kernels as ``[B, Hkv, n_positions, d]`` through strides; rows at or past
 ``length[b]`` are uninitialised and never read. ``Hkv = n_kv_head`` is the model's key / value
-heads: ``n_head`` unless the model uses grouped-query attention.
+heads: ``n_head`` unless the model uses grouped-query attention. A filled cache also takes any
+number of new tokens per row in one step (``mt_flash_attn_extend``: the next turn of a
+conversation, a chunk of a long prompt; ``extend_counts`` builds that step's count vectors).
 """
 from __future__ import annotations
 
@@ -85,6 +87,19 @@ class KVCache:
         if self._visible is None or self._visible[0] != n_new:
             self._visible = (n_new, self.length + n_new)
         return self._visible[1]
+
+    def extend_counts(self, new_len):
+        """Device int32 [B] vectors (visible, q_len) of an extend step that appends new_len[b]
+        real tokens to row b (host counts; the batch is right-padded): the keys each row holds
+        once they are appended, and the counts themselves. Built once per step and shared by the
+        layers, like visible()."""
+        import torch
+        a = np.ascontiguousarray(np.asarray(new_len, dtype=np.int32).reshape(self.batch_size))
+        key = ("extend", a.tobytes())
+        if self._visible is None or self._visible[0] != key:
+            q_len = torch.from_numpy(a).to("cuda")
+            self._visible = (key, self.length + q_len, q_len)
+        return self._visible[1], self._visible[2]
 
     def clamp_to_last_slot(self) -> None:
         """Rows that filled the cache step back to its last slot, on the device (stream-ordered,

@@ -45,6 +45,20 @@ def _kv_tensor(kv_len, batch_size: int, backend):
     return t
 
 
+def _new_token_counts(kv_len, batch_size: int, seq_len: int) -> np.ndarray:
+    """The per-row counts of real new tokens of an extend step as host int64 [B], each in
+    [0, seq_len]."""
+    from .tensor import Tensor
+    a = kv_len.to_numpy() if isinstance(kv_len, Tensor) else kv_len
+    a = np.asarray(a).reshape(-1)
+    if a.size != batch_size:
+        raise ValueError(f"kv_len has {a.size} entries for a batch of {batch_size}")
+    n = a.astype(np.int64)
+    if (n != a).any() or (n < 0).any() or (n > seq_len).any():
+        raise ValueError(f"kv_len must hold whole numbers in [0, {seq_len}] (the new tokens per row), got {a.tolist()}")
+    return n
+
+
 def _positions(seq_len: int, backend):
     key = ("pos", id(backend), seq_len)
     t = _INDEX_CACHE.get(key)
@@ -166,8 +180,10 @@ class MultiHeadAttention(Module):
         x's tokens are appended at the cache's current lengths; an empty cache is a prefill
         (today's causal flash attention over the prompt, kv_len = the prompt lengths of a
         right-padded batch), otherwise x holds at most 8 new tokens per row and attends the
-        cache (Tensor.flash_attention_decode; the cache holds n_kv_head heads). The caller advances the cache's lengths once
-        every layer has run (DecoderLM.forward does)."""
+        cache (Tensor.flash_attention_decode; the cache holds n_kv_head heads). A filled cache
+        with kv_len given is an extend step: x is a right-padded batch of any length whose row b
+        holds kv_len[b] real new tokens (Tensor.flash_attention_extend). The caller advances the
+        cache's lengths once every layer has run (DecoderLM.forward does)."""
         batch_size, seq_len, n_embd = x.shape
         q, k, kT, v = self.project_to_query_key_value(x)
         if cache is None:
@@ -190,6 +206,8 @@ class MultiHeadAttention(Module):
                              f"{kvc.n_kv_head}, {kvc.head_dim}), got ({batch_size}, {num_head}, "
                              f"{self.n_kv_head}, {q_dim})")
         prefill = kvc.empty
+        if not prefill and kv_len is not None:
+            return self._extend_attention(q, k, v, kv_len, lkv)
         if not prefill and seq_len > 8:
             raise ValueError(f"a decode step takes at most 8 new tokens per row, got {seq_len}")
         if int(kvc.length_host.max()) + seq_len > kvc.n_positions:
@@ -199,6 +217,24 @@ class MultiHeadAttention(Module):
         if prefill:
             return self.self_attention(q, k, v, kv_len)
         result = q.flash_attention_decode(lkv.k, lkv.v, kvc.visible(seq_len))
+        result = result.permute(0, 2, 1, 3).contiguous()
+        return result.view(batch_size, seq_len, self.n_embd)
+
+    def _extend_attention(self, q, k, v, kv_len, lkv):
+        """An extend step on a filled cache: kv_len[b] of the seq_len tokens of row b are real
+        (a right-padded batch, any seq_len >= 1). All seq_len projected K / V rows are appended
+        at the cache's lengths (the padding rows land in the stale tail, which is never read, or
+        are dropped past the capacity), then the queries attend the cache
+        (Tensor.flash_attention_extend)."""
+        kvc = lkv.cache
+        batch_size, _, seq_len, _ = q.shape
+        new_len = _new_token_counts(kv_len, batch_size, seq_len)
+        if (kvc.length_host + new_len > kvc.n_positions).any() or seq_len > kvc.n_positions:
+            raise ValueError(f"the new tokens do not fit the KV cache ({kvc.n_positions} positions, "
+                             f"{int(kvc.length_host.max())} held)")
+        visible, q_len = kvc.extend_counts(new_len)
+        q.backend.kv_cache_append(k, v, lkv.k, lkv.v, kvc.length)
+        result = q.flash_attention_extend(lkv.k, lkv.v, visible, q_len)
         result = result.permute(0, 2, 1, 3).contiguous()
         return result.view(batch_size, seq_len, self.n_embd)
 
@@ -295,7 +331,9 @@ class DecoderLM(Module):
         cache: a KVCache (generation). The tokens of idx continue each row at cache.length[b]:
         an empty cache is prefilled with the prompt (kv_len = the prompt lengths), afterwards
         idx holds at most 8 new tokens per row. The cache's lengths advance by kv_len (prefill)
-        or by the number of tokens fed."""
+        or by the number of tokens fed. A filled cache with kv_len given is an extend step
+        (_forward_extend): idx is a right-padded batch of any length, row b holding kv_len[b]
+        (0 <= kv_len[b] <= T) real new tokens; the cache advances by kv_len."""
         if cache is not None:
             return self._forward_cached(idx, kv_len, cache)
         batch_size, seq_len = idx.shape
@@ -321,6 +359,8 @@ class DecoderLM(Module):
             raise ValueError(f"the KV cache was built for {cache.n_layer} layers and a batch of "
                              f"{cache.batch_size}, got {self.n_layer} and {batch_size}")
         prefill = cache.empty
+        if not prefill and kv_len is not None:
+            return self._forward_extend(idx, kv_len, cache)
         if not prefill and seq_len > 8:
             raise ValueError(f"a decode step takes at most 8 new tokens per row, got {seq_len}")
         pos = cache.length_host[:, None] + np.arange(seq_len)[None, :]
@@ -341,8 +381,60 @@ class DecoderLM(Module):
             cache.advance(seq_len)
         return out
 
+    def _forward_extend(self, idx, kv_len, cache):
+        """An extend step: a filled cache and kv_len[b] real new tokens in row b of the
+        right-padded idx [B, T], any T >= 1 (continuing a conversation, a chunk of a long prompt,
+        draft tokens to verify). Row b's tokens take the positions cache.length[b] + i; the cache
+        advances by kv_len. The logits at padding slots are unspecified but finite."""
+        batch_size, seq_len = idx.shape
+        new_len = _new_token_counts(kv_len, batch_size, seq_len)
+        limit = min(self.n_positions, cache.n_positions)
+        if (cache.length_host + new_len > limit).any():
+            b = int(np.argmax(cache.length_host + new_len))
+            raise ValueError(f"row {b} holds {int(cache.length_host[b])} tokens and gets {int(new_len[b])} more: "
+                             f"past n_positions = {limit}")
+        # padding slots only can pass the last position: they take it (their outputs are discarded)
+        pos = np.minimum(cache.length_host[:, None] + np.arange(seq_len)[None, :], self.n_positions - 1)
+        pos = tensor_from_numpy(np.ascontiguousarray(pos, dtype=datatype), backend=self.backend)
+        h = self.token_embeddings(idx) + self.position_embeddings(pos)
+        h = self.dropout(h)
+        for i in range(self.n_layer):
+            h = getattr(self, f"t_layer_{i + 1}")(h, new_len, cache.layer(i))
+        h = self.ln(h.view(batch_size * seq_len, self.n_embd))
+        out = self.lm_head(h).view(batch_size, seq_len, self.n_vocab)
+        cache.advance(new_len)
+        return out
+
+    def _prefill_logits(self, idx, lens, cache, prefill_chunk):
+        """Prefill the right-padded prompts idx [B, T] (lens[b] tokens each) into the empty cache
+        and return (logits, rows) for the choice of every prompt's first new token: rows[b] is
+        the position in logits [B, ., V] that decides row b (None: the only one). prefill_chunk
+        None is one forward over the whole batch; an int C feeds C columns at a time (the first
+        chunk as a prefill of the empty cache, the others as extend steps), so the activations
+        are bounded by C, and gathers the deciding logits rows into one [B, 1, V] device tensor."""
+        if prefill_chunk is None:
+            return self.forward(tensor_from_numpy(idx, backend=self.backend), kv_len=lens.astype(datatype),
+                                cache=cache), lens - 1
+        import torch
+        from .hip_kernel_ops import _torch_view, _wrap
+        B, T = idx.shape
+        first = torch.empty((B, 1, self.n_vocab), dtype=torch.float32, device="cuda")
+        for s in range(0, T, prefill_chunk):
+            width = min(prefill_chunk, T - s)
+            held = np.clip(lens - s, 0, width)
+            logits = self.forward(tensor_from_numpy(np.ascontiguousarray(idx[:, s:s + width]), backend=self.backend),
+                                  kv_len=held.astype(datatype), cache=cache)
+            rows = [b for b in range(B) if s <= lens[b] - 1 < s + width]  # the prompts that end in this chunk
+            if rows:
+                view = _torch_view(logits)
+                r = torch.as_tensor(rows, device=view.device)
+                c = torch.as_tensor([int(lens[b]) - 1 - s for b in rows], device=view.device)
+                first[r, 0] = view[r, c]
+        return _wrap(first.reshape(-1), (B, 1, self.n_vocab), self.backend), None
+
     def generate(self, prompts, max_new_tokens: int, eos_id=None, use_cache: bool = True,
-                 temperature: float = 0.0, top_k: int = 0, seed=None, graph: bool = False, sync_every: int = 8):
+                 temperature: float = 0.0, top_k: int = 0, seed=None, graph: bool = False, sync_every: int = 8,
+                 prefill_chunk=None):
         """Decoding of a list of token-id lists, as the reference's generate
         (project/run_machine_translation.py:271-328); returns the new ids per prompt (without
         the eos that stopped a row). A row also stops once it holds more than n_positions tokens.
@@ -369,7 +461,13 @@ class DecoderLM(Module):
         size, temperature, top_k, eos_id (held by value in the captured launches) and parameter
         storage (held by address: Parameter.update re-captures); graph_captures counts the
         captures. At most MAX_DECODE_GRAPHS graphs per batch size and MAX_DECODE_BATCH_SIZES
-        batch sizes are kept (least recently used go first); drop_decode_graphs() frees them."""
+        batch sizes are kept (least recently used go first); drop_decode_graphs() frees them.
+
+        prefill_chunk=C (needs use_cache=True): the padded prompt batch is prefilled C columns at
+        a time, the first chunk into the empty cache and the others as extend steps on it
+        (Tensor.flash_attention_extend), so the prefill's activations, the [B, C, V] logits among
+        them, are bounded by C instead of the longest prompt. The tokens are those of
+        prefill_chunk=None; a sampled draw still depends on (seed, b) alone."""
         prompts = [[int(t) for t in p] for p in prompts]
         if not prompts or any(len(p) == 0 for p in prompts):
             raise ValueError("generate needs at least one prompt and no empty prompt")
@@ -381,6 +479,12 @@ class DecoderLM(Module):
             raise ValueError(f"temperature must be >= 0, got {temperature}")
         if graph and not use_cache:
             raise ValueError("generate(graph=True) replays the cached decode step: it needs use_cache=True")
+        if prefill_chunk is not None:
+            if not use_cache:
+                raise ValueError("generate(prefill_chunk=...) prefills a KV cache: it needs use_cache=True")
+            if int(prefill_chunk) != prefill_chunk or prefill_chunk < 1:
+                raise ValueError(f"prefill_chunk must be a whole number >= 1, got {prefill_chunk}")
+            prefill_chunk = int(prefill_chunk)
         sampler = None
         if temperature > 0.0 or graph:
             if getattr(self.backend, "select_token", None) is None:
@@ -395,11 +499,12 @@ class DecoderLM(Module):
         self.eval()
         try:
             if graph:
-                return self._generate_graph(prompts, max_new_tokens, eos_id, sampler, max(1, int(sync_every)))
+                return self._generate_graph(prompts, max_new_tokens, eos_id, sampler, max(1, int(sync_every)),
+                                            prefill_chunk)
             if temperature == 0.0:
                 sampler = None
             if use_cache:
-                return self._generate_cached(prompts, max_new_tokens, eos_id, sampler)
+                return self._generate_cached(prompts, max_new_tokens, eos_id, sampler, prefill_chunk)
             return [self._generate_plain(p, max_new_tokens, eos_id, sampler) for p in prompts]
         finally:
             if was_training:
@@ -421,7 +526,7 @@ class DecoderLM(Module):
             new.append(nxt)
         return new
 
-    def _generate_cached(self, prompts, max_new_tokens, eos_id, sampler=None):
+    def _generate_cached(self, prompts, max_new_tokens, eos_id, sampler=None, prefill_chunk=None):
         B = len(prompts)
         lens = np.array([len(p) for p in prompts], dtype=np.int64)
         T = int(lens.max())
@@ -441,8 +546,7 @@ class DecoderLM(Module):
                 return np.argmax(host[np.arange(B), rows] if rows is not None else host[:, 0], axis=-1)
             return self.backend.select_token(logits, sampler[0], sampler[1], sampler[2] + t,
                                              rows=rows)[1].cpu().numpy()
-        nxt = choose(self.forward(tensor_from_numpy(idx, backend=self.backend), kv_len=lens.astype(datatype),
-                                  cache=cache), lens - 1, 0)
+        nxt = choose(*self._prefill_logits(idx, lens, cache, prefill_chunk), 0)
         t = 0
         while True:
             for b in range(B):
@@ -496,7 +600,7 @@ class DecoderLM(Module):
         next such call captures again)."""
         self.__dict__.pop("_decode_graphs", None)
 
-    def _generate_graph(self, prompts, max_new_tokens, eos_id, sampler, sync_every):
+    def _generate_graph(self, prompts, max_new_tokens, eos_id, sampler, sync_every, prefill_chunk=None):
         from .graphs import StepGraph
         if not self.use_flash_attention:
             raise ValueError("a KV cache needs use_flash_attention=True")
@@ -522,9 +626,8 @@ class DecoderLM(Module):
         idx = np.zeros((B, T), dtype=datatype)
         for b, p in enumerate(prompts):
             idx[b, :len(p)] = p
-        logits = self.forward(tensor_from_numpy(idx, backend=self.backend), kv_len=lens.astype(datatype),
-                              cache=st.cache)
-        self.backend.select_token(logits, temperature, top_k, rows=lens - 1, seed_dev=st.seed, eos_id=st.eos_id,
+        logits, rows = self._prefill_logits(idx, lens, st.cache, prefill_chunk)
+        self.backend.select_token(logits, temperature, top_k, rows=rows, seed_dev=st.seed, eos_id=st.eos_id,
                                   out=st.ids_dev, out_i32=st.ids_i32, done=st.done, history=st.history,
                                   step_dev=st.step)
         st.step.add_(1)

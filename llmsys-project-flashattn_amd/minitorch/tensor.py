@@ -360,3 +360,14 @@ class Tensor:
         if fn is None:
             raise NotImplementedError("this backend has no decode attention kernel")
         return fn(self, Kc, Vc, kv_len, causal)
+
+    def flash_attention_extend(self, Kc: "Tensor", Vc: "Tensor", visible=None, q_len=None, causal: bool = True) -> "Tensor":  # noqa: N803
+        """Generation: self holds any number Nq <= Nmax of new query rows [B,H,Nq,d] of a
+        right-padded batch, the first q_len[b] of them real; Kc / Vc are the caches [B,Hkv,Nmax,d],
+        which hold visible[b] rows once the new ones are appended (device count vectors; None: Nmax
+        and Nq). Query i < q_len[b] sits at position visible[b] - q_len[b] + i; rows >= q_len[b]
+        of the result are zero. Inference only: the result has no history."""
+        fn = getattr(self.backend, "flash_attention_extend", None)
+        if fn is None:
+            raise NotImplementedError("this backend has no extend attention kernel")
+        return fn(self, Kc, Vc, visible, q_len, causal)

@@ -130,6 +130,7 @@ class TensorBackend:
         self.flash_attention_causal_bw = ops.flash_attention_causal_bw
         # generation (optional: a backend without the decode kernels has no KV cache)
         self.flash_attention_decode = getattr(ops, "flash_attention_decode", None)
+        self.flash_attention_extend = getattr(ops, "flash_attention_extend", None)
         self.kv_cache_append = getattr(ops, "kv_cache_append", None)
         # the next token chosen on the device (optional: a backend without it keeps the host argmax)
         self.select_token = getattr(ops, "select_token", None)

@@ -36,6 +36,17 @@ alternated in one process like the legs above:
   copy      a device-to-device copy of the gqa leg's own K and V bytes
 
 Each leg rotates over enough cache copies of its own to exceed twice the Infinity Cache.
+
+--extend-legs instead writes profiles/extend_bench.json: per row of EXTEND_ROWS (B, H, Hkv, n, d,
+dtype), 512 new tokens on a cached prefix of n - 512, alternated in one process like the legs above:
+
+  extend    one mt_flash_attn_extend step: the last 512 rows of every sequence against its cache
+  full      mt_flash_attn_fwd_varlen, causal, at N = n with a kv_len vector, K / V repeated to H
+            heads for the grouped-query row: what gives the same rows without the extend step
+  chunked   the whole n tokens as n / 512 extend steps (a chunked prefill; its first step stands in
+            for the prefill of an empty cache, the same arithmetic), against that one-shot forward
+
+The script exits non-zero unless the extend step is faster than the full forward at every row.
 """
 import argparse
 import json
@@ -217,6 +228,98 @@ def gqa_legs(args, torch, _hip):
         raise SystemExit(f"the GQA step is slower than the repeated-K/V step at {slower}")
 
 
+EXTEND_ROWS = [(8, 16, 16, 4096, 64, "f32"), (8, 16, 16, 4096, 64, "bf16"), (8, 16, 4, 4096, 64, "bf16"),
+               (1, 16, 16, 16384, 128, "bf16")]
+EXTEND_NEW = 512
+
+
+def bench_extend(torch, _hip, B, H, Hkv, n, d, name, rounds, warmup, new=EXTEND_NEW):
+    dt = torch.bfloat16 if name == "bf16" else torch.float32
+    es = 2 if name == "bf16" else 4
+    code = 1 if name == "bf16" else 0
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rnd = lambda *s: torch.randn(*s, generator=g, device="cuda", dtype=torch.float32).to(dt)  # noqa: E731
+
+    def make_caches(heads):
+        kv_bytes = 2 * B * heads * n * d * es
+        nset = min(24, max(2, -(-2 * ICACHE // kv_bytes) + 1))
+        return kv_bytes, nset, [(rnd(B, n, heads, d).permute(0, 2, 1, 3), rnd(B, n, heads, d).permute(0, 2, 1, 3))
+                                for _ in range(nset)]
+    kv_bytes, nset, caches = make_caches(Hkv)
+    # the full forward reads K / V of H heads: the caches themselves, or (GQA) K / V repeated to H heads
+    full_bytes, full_nset, full_caches = (kv_bytes, nset, caches) if Hkv == H else make_caches(H)
+    kid, bq, bk = _hip.extend_plan(code, B, H, new, n, d, Hkv=Hkv)
+    q = rnd(B, new, H, d).permute(0, 2, 1, 3)
+    o = torch.empty((B, new, H, d), dtype=dt, device="cuda").permute(0, 2, 1, 3)
+    m, l = (torch.empty((B, H, new), dtype=torch.float32, device="cuda") for _ in range(2))
+    qln = torch.full((B,), new, dtype=torch.int32, device="cuda")
+    kvl = torch.full((B,), n, dtype=torch.int32, device="cuda")
+    chunk_kvl = [torch.full((B,), s + new, dtype=torch.int32, device="cuda") for s in range(0, n, new)]
+    Q = rnd(B, n, H, d).permute(0, 2, 1, 3)
+    O = torch.empty((B, n, H, d), dtype=dt, device="cuda").permute(0, 2, 1, 3)
+    M, Lw = (torch.empty((B, H, n), dtype=torch.float32, device="cuda") for _ in range(2))
+
+    def extend(i):  # the last `new` tokens of every row on the n - new cached ones
+        kc, vc = caches[i % nset]
+        _hip.flash_extend(q, kc, vc, kv_len=kvl, q_len=qln, causal=True, out=o, m=m, l=l)
+
+    def full(i):  # what gives the same rows without the extend step: the whole causal prefill
+        kc, vc = full_caches[i % full_nset]
+        _hip.flash_fwd(Q, kc, vc, True, out=O, m=M, l=Lw, kv_len=kvl)
+
+    def chunked(i):  # the whole row in n / new extend steps (the first on an empty prefix)
+        kc, vc = caches[i % nset]
+        for kv in chunk_kvl:
+            _hip.flash_extend(q, kc, vc, kv_len=kv, q_len=qln, causal=True, out=o, m=m, l=l)
+    legs = {"extend": (extend, 2 * nset), "full": (full, full_nset), "chunked": (chunked, nset)}
+    for fn, inner in legs.values():
+        for _ in range(warmup):
+            _timed(torch, fn, inner)
+    times = {k: [] for k in legs}
+    orders = (("extend", "full", "chunked"), ("full", "chunked", "extend"), ("chunked", "extend", "full"))
+    for r in range(rounds):  # the legs alternate inside every round and swap places between rounds
+        for k in orders[r % 3]:
+            fn, inner = legs[k]
+            times[k].append(_timed(torch, fn, inner))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    spread = {k: (max(v) - min(v)) / med[k] for k, v in times.items()}
+    # multiply-adds of both products, two flops each, over the (query, visible key) pairs
+    pairs_extend = new * (n - new) + new * (new + 1) // 2
+    pairs_full = n * (n + 1) // 2
+    return {
+        "shape": [B, H, n, d], "dtype": name, "kv_heads": Hkv, "new_tokens": new, "cached_prefix": n - new,
+        "kernel": kid, "block_queries": bq, "tile_keys": bk, "workgroups": B * H * -(-new // bq),
+        "kv_bytes": kv_bytes, "cache_sets_rotated": nset, "full_cache_sets_rotated": full_nset, "rounds": rounds,
+        "extend_steps_in_chunked_prefill": len(chunk_kvl),
+        **{f"{k}_s_median": med[k] for k in legs}, **{f"{k}_s_min": min(times[k]) for k in legs},
+        **{f"{k}_s_max": max(times[k]) for k in legs}, **{f"{k}_round_spread": spread[k] for k in legs},
+        "extend_flops": 4 * B * H * d * pairs_extend, "full_flops": 4 * B * H * d * pairs_full,
+        "extend_flops_per_s": 4 * B * H * d * pairs_extend / med["extend"],
+        "full_flops_per_s": 4 * B * H * d * pairs_full / med["full"],
+        "extend_share_of_full_flops": pairs_extend / pairs_full,
+        "extend_over_full_time": med["extend"] / med["full"],
+        "chunked_over_full_time": med["chunked"] / med["full"],
+        # the one condition: the step beats re-prefilling everything, in the same run
+        "extend_faster_than_full": bool(med["extend"] < med["full"]),
+    }
+
+
+def extend_legs(args, torch, _hip):
+    res = {"device": torch.cuda.get_device_name(0), "kernels": []}
+    for B, H, Hkv, n, d, name in EXTEND_ROWS:
+        r = bench_extend(torch, _hip, B, H, Hkv, n, d, name, args.rounds, args.warmup)
+        print(json.dumps(r), flush=True)
+        res["kernels"].append(r)
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(args.extend_out), exist_ok=True)
+    with open(args.extend_out, "w") as f:
+        json.dump(res, f, indent=1)
+    slower = [(r["shape"], r["dtype"], r["kv_heads"], round(r["extend_over_full_time"], 3)) for r in res["kernels"]
+              if not r["extend_faster_than_full"]]
+    if slower:
+        raise SystemExit(f"the extend step is not faster than the full causal forward at {slower}")
+
+
 def bench_generate(minitorch, n_positions, prompt_len, new_tokens, batch, rounds):
     np.random.seed(0)
     backend = minitorch.TensorBackend(minitorch.HipKernelOps)
@@ -320,6 +423,9 @@ def main():
     ap.add_argument("--gqa-legs", action="store_true",
                     help="run the grouped-query decode legs instead, into --gqa-out")
     ap.add_argument("--gqa-out", default=os.path.join(ROOT, "profiles", "decode_gqa_bench.json"))
+    ap.add_argument("--extend-legs", action="store_true",
+                    help="run the extend-attention legs instead, into --extend-out")
+    ap.add_argument("--extend-out", default=os.path.join(ROOT, "profiles", "extend_bench.json"))
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--skip-generate", action="store_true")
@@ -333,6 +439,8 @@ def main():
         return graph_legs(args, torch, minitorch, _hip)
     if args.gqa_legs:
         return gqa_legs(args, torch, _hip)
+    if args.extend_legs:
+        return extend_legs(args, torch, _hip)
     res = {"device": torch.cuda.get_device_name(0), "kernels": [], "generate": []}
     for B, H, L, d, name in SHAPES:
         r = bench_shape(torch, _hip, B, H, L, d, name, args.rounds, args.warmup)
