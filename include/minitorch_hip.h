@@ -272,8 +272,12 @@ int mt_attn_softmax_bw(float* dinp, const float* dout, const float* soft, int64_
 /* Softmax cross-entropy over rows of [rows, classes] fp32 logits (contiguous rows), the
  * reference's softmax_loss (minitorch/nn.py: logsumexp(logits) - logits[target]) in one pass:
  * loss[r] = lse[r] - logits[r, target[r]], lse[r] = log Σ_j exp(logits[r, j]); target holds
- * class ids as floats (minitorch's storage type). Backward:
- * dlogits[r, j] = dloss[r] (exp(logits[r, j] - lse[r]) - [j == target[r]]). */
+ * class ids as floats (minitorch's storage type; truncated toward zero). A target outside
+ * [0, classes) picks nothing: loss[r] = lse[r] and the backward subtracts no one-hot. Backward:
+ * dlogits[r, j] = dloss[r] (exp(logits[r, j] - lse[r]) - [j == target[r]]).
+ * -inf logits are allowed (a mask on banned classes) and weigh zero: they add nothing to lse and
+ * their dlogits are 0, whichever kernel the class count and alignment select. A row of only
+ * -inf, or one holding +inf or NaN, is unspecified. */
 int mt_softmax_xent_fw(float* loss, float* lse, const float* logits, const float* target, int64_t rows,
                        int64_t classes, void* stream);
 int mt_softmax_xent_bw(float* dlogits, const float* dloss, const float* logits, const float* target,
@@ -357,7 +361,9 @@ int mt_dropout_dseed(float* out, const float* x, int64_t n, float p, float scale
 
 /* Embedding rows (reference minitorch/modules_basic.py Embedding.forward: one_hot(ids, V) @ W),
  * fp32, ids[ntok] the float token ids, W [V x E] and out / dout [ntok x E] contiguous:
- *   mt_embedding_fw: out[t] = W[ids[t]]            (a zero row for an id outside [0, V))
+ * A float id f names row trunc(f) iff f >= 0 and trunc(f) < V (-0.0 and 0.9 name row 0); every
+ * other value (negative, >= V however large, +-inf, NaN) names none and never indexes memory.
+ *   mt_embedding_fw: out[t] = W[ids[t]]            (a row of +0.0 for an id that names none)
  *   mt_embedding_bw: dW[v]  = sum over t with ids[t] == v of dout[t] in a fixed order
  *                    (deterministic); every row of dW is written (zero for ids that do not occur) */
 int mt_embedding_fw(float* out, const float* ids, const float* weight, int64_t ntok, int64_t V, int64_t E,
@@ -372,7 +378,8 @@ int mt_embedding_bw(float* dweight, const float* dout, const float* ids, int64_t
  * 1 - b1, 1 - b2, eps and step_size are each rounded to fp32 once; the update divides by
  * (powf(v, 0.5) + eps) through its reciprocal, as the tensor ops do (bit-identical). Replaces the
  * reference's per-parameter tensor-op Adam (minitorch/optim.py:52-75), one launch per 24
- * tensors. */
+ * tensors. A tensor of 0 elements is skipped and its pointers are not looked at; a NULL pointer
+ * of a tensor with elements is an error (tensors of earlier launches are already updated). */
 int mt_adam_step(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
                  float* const* exp_avg_sq, const int64_t* numels, double beta1, double beta2, double eps,
                  double step_size, void* stream);

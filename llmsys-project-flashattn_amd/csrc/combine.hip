@@ -1026,12 +1026,17 @@ __global__ void rand_uniform_kernel(float* out, int64_t n, uint64_t seed) {
 // uniform above (u > p keeps, as rand(shape) > p does) and redrawn in the backward from the
 // same seed, so no mask is stored. Rows of `cols` contiguous floats; 16 B per lane where the
 // row length allows.
+// The fused multiply-adds are written out and contraction is off, so the float4 loop and the
+// scalar loop of bias_gelu_kernel round alike: left to the compiler, the float4 loop fused
+// 1 - t t and 1 + 3c u^2 (one rounding, as written here) and the scalar loop did not, and the two
+// paths' dx differed where tanh is near +-1.
 __device__ __forceinline__ float gelu_tanh(float u, float& t, float& dt) {
+#pragma clang fp contract(off)
   constexpr float k = 0.7978845608028654f;  // sqrt(2 / pi)
   const float u2 = u * u;
-  t = tanhf(k * (u + 0.044715f * (u2 * u)));
-  dt = k * (1.f + 3.f * 0.044715f * u2);   // d(inner)/du
-  return 0.5f * u * (1.f + t);
+  t = tanhf(k * fmaf(0.044715f, u2 * u, u));
+  dt = k * fmaf(3.f * 0.044715f, u2, 1.f);  // d(inner)/du
+  return (0.5f * u) * (1.f + t);
 }
 template <bool BW>
 __global__ __launch_bounds__(256) void bias_gelu_kernel(float* __restrict__ out, const float* __restrict__ x,
@@ -1040,12 +1045,13 @@ __global__ __launch_bounds__(256) void bias_gelu_kernel(float* __restrict__ out,
                                                         int vec) {
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
   auto one = [&](float xv, float bv, float g) -> float {
+#pragma clang fp contract(off)
     float t, dt;
     const float u = xv + bv;
     const float y = gelu_tanh(u, t, dt);
     if (!BW) return y;
     // d/du 0.5 u (1 + t) = 0.5 (1 + t) + 0.5 u (1 - t^2) dt
-    return g * (0.5f * (1.f + t) + 0.5f * u * (1.f - t * t) * dt);
+    return g * fmaf(0.5f, 1.f + t, dt * ((0.5f * u) * fmaf(-t, t, 1.f)));
   };
   if (vec) {  // cols % 4 == 0, 16-B aligned rows
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n / 4; i += step) {
@@ -1077,15 +1083,20 @@ __global__ __launch_bounds__(256) void dropout_kernel(float* __restrict__ out, c
 // [V x E] product): the forward gathers W[id] (zero for an id outside [0, V), the one-hot
 // row of such an id being zero); the backward sums dY rows into dW rows. ids are the float
 // token ids of the minitorch tensor.
+// The row a float id names, -1 for one that names none. The range is tested on the float: the
+// conversion of f >= 2^63 (1e30, +inf) is not defined, and what gfx950 computes for it is
+// negative (high word saturated to 0xffffffff), which `id < V` alone let through as a row index.
+__device__ __forceinline__ int64_t embed_id(float f) {
+  return (f >= 0.f && f < 9223372036854775808.f) ? (int64_t)f : -1;
+}
 __global__ __launch_bounds__(256) void embed_fw_kernel(float* __restrict__ out, const float* __restrict__ ids,
                                                        const float* __restrict__ w, int64_t ntok, int64_t V,
                                                        int64_t E) {
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ntok * E; i += step) {
     const int64_t t = i / E, c = i - t * E;
-    const float f = ids[t];
-    const int64_t id = (int64_t)f;
-    out[i] = (f >= 0.f && id < V) ? w[id * E + c] : 0.f;
+    const int64_t id = embed_id(ids[t]);
+    out[i] = (id >= 0 && id < V) ? w[id * E + c] : 0.f;
   }
 }
 // dW[v] = sum of dY[t] over the tokens t with id v (deterministic: fixed order; every row of
@@ -1118,9 +1129,8 @@ __global__ __launch_bounds__(1024) void embed_bw_kernel(float* __restrict__ dw, 
         const int64_t t = t0 + w * kW + k + lane;
         int rel = -1;
         if (t < ntok) {
-          const float f = ids[t];
-          const int64_t id = (int64_t)f;
-          if (f >= 0.f && id >= v0 && id < v0 + kEmbVB) rel = (int)(id - v0);
+          const int64_t id = embed_id(ids[t]);
+          if (id >= v0 && id < v0 + kEmbVB) rel = (int)(id - v0);
         }
         const unsigned long long m = __ballot(rel >= 0);
         if (rel >= 0) my[n + __popcll(m & ((1ull << lane) - 1))] = (w * kW + k + lane) | (rel << 12);

@@ -650,6 +650,9 @@ __device__ __forceinline__ void lse_add(float& m, float& s, float x) {
     s = (m == -INFINITY ? 0.f : s * expf(m - x)) + 1.f;
     m = x;
   } else {
+    // x = -inf while m is still -inf makes s NaN (expf(-inf + inf)); that s is never used: the
+    // branch above and lse_merge both drop the sum of a pair whose m is -inf, so -inf logits
+    // weigh zero here as in xent_fw_reg_kernel (tests/test_train_kernels_gpu.py)
     s += expf(x - m);
   }
 }
