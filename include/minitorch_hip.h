@@ -207,6 +207,59 @@ int mt_kv_cache_append(int dtype, const void* k_new, const void* v_new, void* k_
                        const int64_t* kcache_strides, const int64_t* vcache_strides,
                        const int* pos, void* stream);
 
+/* ---- quantised KV cache ------------------------------------------------------
+ * K and V stored as bf16 (MT_KV_BF16) or as one byte of OCP e4m3 (MT_KV_FP8: "e4m3fn", bias 7,
+ * max 448, no inf, NaN = 0x7F / 0xFF) with one fp32 scale per cached row: a row's values are
+ * scale * e4m3(code). Queries, arithmetic, O, m and l stay fp32.
+ *   k_cache, v_cache:  [B, Hkv, Nmax, d] through strides in storage elements (bf16, or bytes),
+ *                      NULL = contiguous
+ *   k_scale, v_scale:  fp8: dense fp32 [B, Hkv, Nmax]; bf16: ignored (pass NULL)
+ * Requires d % 8 == 0, d <= 256, unit-stride d, and every row start (base pointer and strides) a
+ * multiple of 8 bytes for fp8 and of 16 bytes for bf16. Refused with a status and a
+ * mt_last_error() message before any device call: an unknown kv_dtype, fp8 with a NULL scale
+ * pointer, d % 8, d > 256, non-positive sizes, misaligned pointers or strides, and for decode Nq
+ * outside 1..8, Hkv not dividing H and a workspace below ..._workspace_bytes.
+ *
+ * mt_kv_cache_append_quant: mt_kv_cache_append's footprint (rows pos[b] .. pos[b] + Nq - 1 of
+ * every (b, hkv); rows outside [0, Nmax) dropped; nothing else in the caches or the scales is
+ * written) from fp32 new rows [B, Hkv, Nq, d] of any 4-B aligned strides (unit-stride d).
+ * bf16: round to nearest even. fp8: amax = the largest |x| of the row's d elements,
+ * s = amax > 0 ? amax / 448 : 1, codes = e4m3 round-to-nearest of x / s (fp32 division), s stored
+ * at the row's scale slot; a row holding an inf or a NaN is stored as NaN codes (0x7F) with a NaN
+ * scale. Plain vector stores, no atomics.
+ *
+ * mt_flash_attn_decode_kvq: mt_flash_attn_decode_gqa's contract (Nq <= 8, bottom-right causal
+ * alignment, (0, -inf, 0) for a query with no visible key, rows >= n never loaded and their
+ * scales neither, row packing, two plain launches, fixed-order combine, the same workspace
+ * layout) with fp32 q / o / m / l ([B, H, Nq, d], 16-B rows) and quantised caches. Both formats
+ * are read in chunks of 8 elements, so the plan (splits, span, tile, packing) is the one
+ * mt_flash_attn_decode_gqa_splits gives for MT_BF16 at the same sizes: a function of the sizes
+ * only.
+ *
+ * mt_kv_cache_dequant: writes the fp32 rows j < clamp(kv_len[b], 0, Nk) (kv_len NULL: Nk) of
+ * k_out / v_out ([B, Hkv, Nk, d] through strides in elements, 16-B rows): bf16 widened, fp8
+ * e4m3(code) * scale (one fp32 product). Rows at or past that count are neither read nor written. */
+enum { MT_KV_BF16 = 1, MT_KV_FP8 = 2 };
+int mt_flash_attn_decode_kvq_splits(int kv_dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk,
+                                    int64_t d, int64_t* span_keys, int64_t* tile_keys);
+int64_t mt_flash_attn_decode_kvq_workspace_bytes(int kv_dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq,
+                                                 int64_t Nk, int64_t d);
+int mt_flash_attn_decode_kvq(int kv_dtype, int causal, const void* q, const void* k_cache, const void* v_cache,
+                             const float* k_scale, const float* v_scale, void* o, float* m, float* l,
+                             int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d,
+                             const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                             const int64_t* o_strides, const int* kv_len,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+int mt_kv_cache_append_quant(int kv_dtype, const float* k_new, const float* v_new, void* k_cache, void* v_cache,
+                             float* k_scale, float* v_scale, int64_t B, int64_t Hkv, int64_t Nq, int64_t Nmax,
+                             int64_t d, const int64_t* knew_strides, const int64_t* vnew_strides,
+                             const int64_t* kcache_strides, const int64_t* vcache_strides,
+                             const int* pos, void* stream);
+int mt_kv_cache_dequant(int kv_dtype, const void* k_cache, const void* v_cache, const float* k_scale,
+                        const float* v_scale, float* k_out, float* v_out, int64_t B, int64_t Hkv, int64_t Nk,
+                        int64_t d, const int64_t* kcache_strides, const int64_t* vcache_strides,
+                        const int64_t* kout_strides, const int64_t* vout_strides, const int* kv_len, void* stream);
+
 /* ---- generation: the next token chosen on the device ------------------------
  * One id per row of the fp32 logits [B, V] (rows row_stride >= V elements apart, unit-stride
  * columns; what lies between the rows is never read). Stream-ordered, allocates nothing, does

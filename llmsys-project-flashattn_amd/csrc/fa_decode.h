@@ -1,4 +1,5 @@
-// Shared between fa_decode.hip (kernels, launchers) and capi_decode.hip (the C ABI).
+// Shared between fa_decode.hip (kernels, launchers), fa_kvq.hip (the quantised-cache kernels, which
+// reuse the lane-group helpers and the combine pass) and capi_decode.hip / capi_kvq.hip (the C ABI).
 #pragma once
 #include "fa_common.h"
 
@@ -26,10 +27,42 @@ struct AppendArgs {
   int H, Nq, Nmax, chunks, esize;
 };
 
+int decode_lpk(int64_t d, int esize);  // lanes per key: the power of two >= 16-B chunks per row, at least 4
 DecodePlan decode_plan(int esize, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d);
 hipError_t launch_decode(const DecodeArgs& a, bool bf16_in, int64_t B, hipStream_t st);
+hipError_t launch_decode_combine(const DecodeArgs& a, int64_t B, hipStream_t st);  // pass 2 alone
 hipError_t launch_kv_append(const AppendArgs& a, hipStream_t st);
 int set_error(const char* fmt, ...);           // capi_flash.hip
 int check_hip(hipError_t e, const char* where);
+
+constexpr int kDecWaves = 4;    // waves per workgroup
+constexpr int kDecUnroll = 4;   // key loads of K (and of V) in flight per wave and step
+
+__device__ __forceinline__ float dpp_f(float x, const int ctrl_sel) {
+  // DPP controls: 0xB1 quad_perm [1,0,3,2], 0x4E quad_perm [2,3,0,1], 0x141 row_half_mirror,
+  // 0x140 row_mirror
+  int v = __builtin_bit_cast(int, x), r;
+  switch (ctrl_sel) {
+    case 0: r = __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true); break;
+    case 1: r = __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true); break;
+    case 2: r = __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true); break;
+    default: r = __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true); break;
+  }
+  return __builtin_bit_cast(float, r);
+}
+
+// the sum of v over the LPK lanes of a key group, in every lane of the group (after each step
+// the value is uniform over the lanes already joined, so the mirrors pair the two halves)
+template <int LPK> __device__ __forceinline__ float group_sum(float v) {
+  v += dpp_f(v, 0);
+  v += dpp_f(v, 1);
+  if (LPK >= 8) v += dpp_f(v, 2);
+  if (LPK >= 16) v += dpp_f(v, 3);
+  if (LPK >= 32) v += __shfl_xor(v, 16);
+  if (LPK >= 64) v += __shfl_xor(v, 32);
+  return v;
+}
+
+__device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
 
 }  // namespace mt

@@ -39,12 +39,10 @@
 
 namespace mt {
 
-constexpr int kDecWaves = 4;    // waves per workgroup
-constexpr int kDecUnroll = 4;   // key loads of K (and of V) in flight per wave and step
 constexpr int kDecTargetWgs = 1024;  // 4 workgroups per CU when B*H alone is short of that
 
 // lanes per key: the power of two >= chunks per row, at least 4
-static int decode_lpk(int64_t d, int esize) {
+int decode_lpk(int64_t d, int esize) {
   const int c = (int)(d * esize / 16);
   int l = 4;
   while (l < c) l *= 2;
@@ -74,31 +72,6 @@ DecodePlan decode_plan(int esize, int64_t B, int64_t H, int64_t Hkv, int64_t Nq,
   return p;
 }
 
-__device__ __forceinline__ float dpp_f(float x, const int ctrl_sel) {
-  // DPP controls: 0xB1 quad_perm [1,0,3,2], 0x4E quad_perm [2,3,0,1], 0x141 row_half_mirror,
-  // 0x140 row_mirror
-  int v = __builtin_bit_cast(int, x), r;
-  switch (ctrl_sel) {
-    case 0: r = __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true); break;
-    case 1: r = __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true); break;
-    case 2: r = __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true); break;
-    default: r = __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true); break;
-  }
-  return __builtin_bit_cast(float, r);
-}
-
-// the sum of v over the LPK lanes of a key group, in every lane of the group (after each step
-// the value is uniform over the lanes already joined, so the mirrors pair the two halves)
-template <int LPK> __device__ __forceinline__ float group_sum(float v) {
-  v += dpp_f(v, 0);
-  v += dpp_f(v, 1);
-  if (LPK >= 8) v += dpp_f(v, 2);
-  if (LPK >= 16) v += dpp_f(v, 3);
-  if (LPK >= 32) v += __shfl_xor(v, 16);
-  if (LPK >= 64) v += __shfl_xor(v, 32);
-  return v;
-}
-
 template <typename T> struct Chunk;
 template <> struct Chunk<float> {
   static constexpr int N = 4;
@@ -118,8 +91,6 @@ template <> struct Chunk<bf16> {
     }
   }
 };
-
-__device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // 4 consecutive O elements of one row: fp32 (16-B store) or bf16 (8-B store)
 __device__ __forceinline__ void store_o4(void* o, int o_f32, int64_t e, const float4& x) {
@@ -417,6 +388,10 @@ hipError_t launch_decode(const DecodeArgs& a, bool bf16_in, int64_t B, hipStream
   const dim3 grid((unsigned)(B * a.Hkv * a.slices), (unsigned)a.nsplit);
   hipError_t e = bf16_in ? launch_partial<bf16>(a, lpk, grid, st) : launch_partial<float>(a, lpk, grid, st);
   if (e != hipSuccess || a.nsplit == 1) return e;
+  return launch_decode_combine(a, B, st);
+}
+
+hipError_t launch_decode_combine(const DecodeArgs& a, int64_t B, hipStream_t st) {
   fa_decode_combine<<<dim3((unsigned)(B * a.H * a.Nq)), 64, 0, st>>>(a);
   return hipGetLastError();
 }

@@ -22,6 +22,9 @@ LIB_PATH = os.environ.get("MT_HIP_LIB") or os.path.join(_HERE, "_lib", "libminit
 
 MT_F32 = 0
 MT_BF16 = 1
+# storage formats of a quantised KV cache (kv_dtype of the mt_*_kvq / *_quant entry points)
+MT_KV_BF16 = 1
+MT_KV_FP8 = 2
 
 _lib = None
 
@@ -65,6 +68,14 @@ _PROTOS = {
                                     _i64p, _i64p, _i64p, _i64p, _vp, _vp, _vp]),
     "mt_kv_cache_append": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                   _i64p, _i64p, _i64p, _i64p, _vp, _vp]),
+    "mt_flash_attn_decode_kvq_splits": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64p, _i64p]),
+    "mt_flash_attn_decode_kvq_workspace_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64, _i64]),
+    "mt_flash_attn_decode_kvq": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64,
+                                        _i64, _i64, _i64p, _i64p, _i64p, _i64p, _vp, _vp, _i64, _vp]),
+    "mt_kv_cache_append_quant": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                        _i64p, _i64p, _i64p, _i64p, _vp, _vp]),
+    "mt_kv_cache_dequant": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64,
+                                   _i64p, _i64p, _i64p, _i64p, _vp, _vp]),
     "mt_select_token": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _i64, ctypes.c_uint64, _vp, _i64,
                                _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "mt_attn_softmax_fw": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64p, _int, _vp]),
@@ -460,6 +471,141 @@ def kv_cache_append(k_new, v_new, k_cache, v_cache, pos, stream: Optional[int] =
         dtype_code(k_new), k_new.data_ptr(), v_new.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
         B, H, Nq, Nmax, d, strides3(k_new), strides3(v_new), strides3(k_cache), strides3(v_cache),
         p.data_ptr(), st), "mt_kv_cache_append")
+
+
+# ---- quantised KV cache (mt_kv_cache_append_quant / mt_flash_attn_decode_kvq / mt_kv_cache_dequant) ----
+def kv_code(cache) -> int:
+    """The kv_dtype code of a quantised cache tensor: torch.bfloat16 -> MT_KV_BF16, torch.uint8
+    (one e4m3 code per byte) -> MT_KV_FP8."""
+    torch = _torch()
+    if cache.dtype == torch.bfloat16:
+        return MT_KV_BF16
+    if cache.dtype == torch.uint8:
+        return MT_KV_FP8
+    raise TypeError(f"a quantised cache is torch.bfloat16 or torch.uint8 (e4m3 codes), got {cache.dtype}")
+
+
+def _kvq_caches(name, k_cache, v_cache, k_scale, v_scale, B, d):
+    """Checks shared by the three entry points; returns (code, Hkv, N, k_scale ptr, v_scale ptr)."""
+    torch = _torch()
+    code = kv_code(k_cache)
+    if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or v_cache.dtype != k_cache.dtype:
+        raise ValueError(f"{name}: the caches must be two [B,Hkv,N,d] tensors of one dtype")
+    _, Hkv, N, dc = k_cache.shape
+    if k_cache.shape[0] != B or dc != d:
+        raise ValueError(f"{name}: cache shape {tuple(k_cache.shape)} does not match (B, d) = ({B}, {d})")
+    if d > 1 and (k_cache.stride(3) != 1 or v_cache.stride(3) != 1):
+        raise ValueError(f"{name}: the caches need a unit-stride last dim")
+    if code == MT_KV_BF16:
+        return code, Hkv, N, None, None
+    for nm, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if s is None:
+            raise ValueError(f"{name}: an fp8 cache needs {nm}")
+        if (not s.is_cuda or s.dtype != torch.float32 or tuple(s.shape) != (B, Hkv, N) or not s.is_contiguous()):
+            raise ValueError(f"{name}: {nm} must be a contiguous device float32 [{B}, {Hkv}, {N}] tensor")
+    return code, Hkv, N, k_scale.data_ptr(), v_scale.data_ptr()
+
+
+def decode_kvq_splits(kv_dtype: int, B: int, H: int, Nq: int, Nk: int, d: int, Hkv: Optional[int] = None):
+    """(splits, span_keys, tile_keys) of mt_flash_attn_decode_kvq: decode_splits' answer for a bf16
+    cache at the same sizes, whatever the format (both are read in chunks of 8 elements)."""
+    span, tile = ctypes.c_int64(0), ctypes.c_int64(0)
+    n = lib().mt_flash_attn_decode_kvq_splits(kv_dtype, B, H, H if Hkv is None else Hkv, Nq, Nk, d,
+                                              ctypes.byref(span), ctypes.byref(tile))
+    if n <= 0:
+        raise ValueError(lib().mt_last_error().decode(errors="replace"))
+    return n, span.value, tile.value
+
+
+def decode_kvq_workspace_bytes(kv_dtype: int, B: int, H: int, Nq: int, Nk: int, d: int,
+                               Hkv: Optional[int] = None) -> int:
+    n = lib().mt_flash_attn_decode_kvq_workspace_bytes(kv_dtype, B, H, H if Hkv is None else Hkv, Nq, Nk, d)
+    if n < 0:
+        raise ValueError(lib().mt_last_error().decode(errors="replace"))
+    return int(n)
+
+
+def kv_cache_append_quant(k_new, v_new, k_cache, v_cache, pos, k_scale=None, v_scale=None,
+                          stream: Optional[int] = None) -> None:
+    """Quantise the fp32 new rows k_new / v_new [B,Hkv,Nq,d] into the caches [B,Hkv,Nmax,d]
+    (torch.bfloat16, or torch.uint8 e4m3 codes with the fp32 row scales k_scale / v_scale
+    [B,Hkv,Nmax]) at rows pos[b] .. pos[b] + Nq - 1 (rows past the capacity are dropped)."""
+    torch = _torch()
+    _check_dev(k_new, v_new, k_cache, v_cache)
+    B, Hkv, Nq, d = k_new.shape
+    if v_new.shape != k_new.shape or k_new.dtype != torch.float32 or v_new.dtype != torch.float32:
+        raise ValueError("kv_cache_append_quant: the new rows must be two float32 [B,Hkv,Nq,d] tensors")
+    code, Hc, Nmax, ksp, vsp = _kvq_caches("kv_cache_append_quant", k_cache, v_cache, k_scale, v_scale, B, d)
+    if Hc != Hkv:
+        raise ValueError("kv_cache_append_quant: shapes do not match")
+    p = _kv_arg(pos, B, k_new.device)
+    st = stream_ptr(k_new.device) if stream is None else stream
+    check(lib().mt_kv_cache_append_quant(
+        code, k_new.data_ptr(), v_new.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), ksp, vsp,
+        B, Hkv, Nq, Nmax, d, strides3(k_new), strides3(v_new), strides3(k_cache), strides3(v_cache),
+        p.data_ptr(), st), "mt_kv_cache_append_quant")
+
+
+def flash_decode_kvq(q, k_cache, v_cache, k_scale=None, v_scale=None, kv_len=None, causal: bool = True,
+                     out=None, m=None, l=None, workspace=None, stream: Optional[int] = None):
+    """Decode attention on a quantised cache (mt_flash_attn_decode_kvq): flash_decode's contract
+    with an fp32 q [B,H,Nq,d], fp32 (O, m, l) and the caches [B,Hkv,Nk,d] as torch.bfloat16, or
+    torch.uint8 e4m3 codes with the fp32 row scales [B,Hkv,Nk]. workspace: a device buffer of at
+    least decode_kvq_workspace_bytes (allocated when None)."""
+    torch = _torch()
+    _check_dev(q, k_cache, v_cache)
+    B, H, Nq, d = q.shape
+    if q.dtype != torch.float32:
+        raise TypeError("flash_decode_kvq takes float32 queries")
+    code, Hkv, Nk, ksp, vsp = _kvq_caches("flash_decode_kvq", k_cache, v_cache, k_scale, v_scale, B, d)
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"the caches' {Hkv} heads do not divide q's {H} heads")
+    if out is None:
+        out = torch.empty((B, H, Nq, d), dtype=torch.float32, device=q.device)
+    elif out.dtype != torch.float32:
+        raise TypeError("flash_decode_kvq writes a float32 O")
+    if m is None:
+        m = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    if l is None:
+        l = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    need = lib().mt_flash_attn_decode_kvq_workspace_bytes(code, B, H, Hkv, Nq, Nk, d)
+    if workspace is None and need > 0:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=q.device)
+    kv = _kv_arg(kv_len, B, q.device)
+    st = stream_ptr(q.device) if stream is None else stream
+    check(lib().mt_flash_attn_decode_kvq(
+        code, int(causal), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), ksp, vsp, out.data_ptr(),
+        m.data_ptr(), l.data_ptr(), B, H, Hkv, Nq, Nk, d, strides3(q), strides3(k_cache), strides3(v_cache),
+        strides3(out), None if kv is None else kv.data_ptr(),
+        None if workspace is None else workspace.data_ptr(),
+        0 if workspace is None else workspace.numel() * workspace.element_size(), st),
+        "mt_flash_attn_decode_kvq")
+    return out, m, l
+
+
+def kv_cache_dequant(k_cache, v_cache, k_scale=None, v_scale=None, kv_len=None, k_out=None, v_out=None,
+                     stream: Optional[int] = None):
+    """The fp32 values of the first kv_len[b] rows (None: all) of a quantised cache
+    (mt_kv_cache_dequant) written to k_out / v_out [B,Hkv,Nk,d] float32 (allocated, uninitialised
+    past those rows, when None); the other rows are neither read nor written. Returns them."""
+    torch = _torch()
+    _check_dev(k_cache, v_cache)
+    B, d = k_cache.shape[0], k_cache.shape[3]
+    code, Hkv, Nk, ksp, vsp = _kvq_caches("kv_cache_dequant", k_cache, v_cache, k_scale, v_scale, B, d)
+    if k_out is None:
+        k_out = torch.empty((B, Hkv, Nk, d), dtype=torch.float32, device=k_cache.device)
+    if v_out is None:
+        v_out = torch.empty((B, Hkv, Nk, d), dtype=torch.float32, device=k_cache.device)
+    for t in (k_out, v_out):
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, Hkv, Nk, d):
+            raise ValueError(f"kv_cache_dequant: outputs must be float32 [{B}, {Hkv}, {Nk}, {d}] tensors")
+    kv = _kv_arg(kv_len, B, k_cache.device)
+    st = stream_ptr(k_cache.device) if stream is None else stream
+    check(lib().mt_kv_cache_dequant(
+        code, k_cache.data_ptr(), v_cache.data_ptr(), ksp, vsp, k_out.data_ptr(), v_out.data_ptr(),
+        B, Hkv, Nk, d, strides3(k_cache), strides3(v_cache), strides3(k_out), strides3(v_out),
+        None if kv is None else kv.data_ptr(), st), "mt_kv_cache_dequant")
+    return k_out, v_out
 
 
 def rand_uniform(n: int, seed: int, out=None, stream: Optional[int] = None):

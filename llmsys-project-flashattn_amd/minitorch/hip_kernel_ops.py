@@ -541,6 +541,38 @@ class HipKernelOps(TensorOps):
         _hip.kv_cache_append(_torch_view(Knew), _torch_view(Vnew), _torch_view(Kc), _torch_view(Vc),
                              HipKernelOps._i32(pos))
 
+    # ---- quantised KV cache: the caches and scales are torch tensors (bf16, or uint8 e4m3 codes) ----
+    @staticmethod
+    def kv_cache_append_quant(Knew: Tensor, Vnew: Tensor, kc, vc, pos, k_scale=None, v_scale=None) -> None:
+        """Quantise the fp32 new rows Knew / Vnew [B,Hkv,Nq,d] into the torch caches kc / vc
+        [B,Hkv,Nmax,d] at rows pos[b] .. (mt_kv_cache_append_quant; k_scale / v_scale: the fp8
+        row scales)."""
+        _hip.kv_cache_append_quant(_torch_view(Knew), _torch_view(Vnew), kc, vc, HipKernelOps._i32(pos),
+                                   k_scale, v_scale)
+
+    @staticmethod
+    def flash_attention_decode_kvq(Q: Tensor, kc, vc, k_scale=None, v_scale=None, kv_len=None,
+                                   causal: bool = True, workspace=None) -> Tensor:
+        """flash_attention_decode on a quantised cache (mt_flash_attn_decode_kvq): fp32 Q and O,
+        the torch caches kc / vc [B,Hkv,Nmax,d] in bf16 or e4m3 codes with their row scales.
+        workspace: a torch fp32 buffer of _hip.decode_kvq_workspace_bytes (allocated when None)."""
+        import torch
+        B, H, Nq, d = Q.shape
+        so = _layout_like(Q)
+        o = torch.empty(B * H * Nq * d, dtype=torch.float32, device="cuda")
+        _hip.flash_decode_kvq(_torch_view(Q), kc, vc, k_scale, v_scale,
+                              kv_len=None if kv_len is None else HipKernelOps._i32(kv_len), causal=causal,
+                              out=torch.as_strided(o, (B, H, Nq, d), so), workspace=workspace)
+        return _wrap(o, (B, H, Nq, d), Q.backend, so)
+
+    @staticmethod
+    def kv_cache_dequant(kc, vc, k_scale, v_scale, kv_len, Kout: Tensor, Vout: Tensor) -> None:
+        """The fp32 values of the first kv_len[b] rows of the quantised torch caches written into
+        the fp32 tensors Kout / Vout [B,Hkv,Nmax,d] (mt_kv_cache_dequant)."""
+        _hip.kv_cache_dequant(kc, vc, k_scale, v_scale,
+                              kv_len=None if kv_len is None else HipKernelOps._i32(kv_len),
+                              k_out=_torch_view(Kout), v_out=_torch_view(Vout))
+
     @staticmethod
     def select_token(logits: Tensor, temperature: float = 0.0, top_k: int = 0, seed: int = 0, rows=None, **kw):
         """The next token ids chosen on the device (mt_select_token) from logits [B, V], or from

@@ -213,10 +213,18 @@ class MultiHeadAttention(Module):
         if int(kvc.length_host.max()) + seq_len > kvc.n_positions:
             raise ValueError(f"{seq_len} new tokens do not fit the KV cache ({kvc.n_positions} positions, "
                              f"{int(kvc.length_host.max())} held)")
-        q.backend.kv_cache_append(k, v, lkv.k, lkv.v, kvc.length)
+        if kvc.quantised:
+            # the rows are quantised as they land; a prefill still attends the fresh fp32 K / V
+            q.backend.kv_cache_append_quant(k, v, lkv.k, lkv.v, kvc.length, lkv.k_scale, lkv.v_scale)
+        else:
+            q.backend.kv_cache_append(k, v, lkv.k, lkv.v, kvc.length)
         if prefill:
             return self.self_attention(q, k, v, kv_len)
-        result = q.flash_attention_decode(lkv.k, lkv.v, kvc.visible(seq_len))
+        if kvc.quantised:
+            result = q.backend.flash_attention_decode_kvq(q, lkv.k, lkv.v, lkv.k_scale, lkv.v_scale,
+                                                          kvc.visible(seq_len), True, kvc.decode_workspace(seq_len))
+        else:
+            result = q.flash_attention_decode(lkv.k, lkv.v, kvc.visible(seq_len))
         result = result.permute(0, 2, 1, 3).contiguous()
         return result.view(batch_size, seq_len, self.n_embd)
 
@@ -233,8 +241,16 @@ class MultiHeadAttention(Module):
             raise ValueError(f"the new tokens do not fit the KV cache ({kvc.n_positions} positions, "
                              f"{int(kvc.length_host.max())} held)")
         visible, q_len = kvc.extend_counts(new_len)
-        q.backend.kv_cache_append(k, v, lkv.k, lkv.v, kvc.length)
-        result = q.flash_attention_extend(lkv.k, lkv.v, visible, q_len)
+        if kvc.quantised:
+            # no extend kernel reads a quantised cache: the visible rows (the new ones included) are
+            # dequantised into the cache's fp32 scratch, one extra fp32 write and read of them
+            q.backend.kv_cache_append_quant(k, v, lkv.k, lkv.v, kvc.length, lkv.k_scale, lkv.v_scale)
+            ks, vs = kvc.scratch()
+            q.backend.kv_cache_dequant(lkv.k, lkv.v, lkv.k_scale, lkv.v_scale, visible, ks, vs)
+            result = q.flash_attention_extend(ks, vs, visible, q_len)
+        else:
+            q.backend.kv_cache_append(k, v, lkv.k, lkv.v, kvc.length)
+            result = q.flash_attention_extend(lkv.k, lkv.v, visible, q_len)
         result = result.permute(0, 2, 1, 3).contiguous()
         return result.view(batch_size, seq_len, self.n_embd)
 
@@ -345,11 +361,12 @@ class DecoderLM(Module):
         h = self.ln(h.view(batch_size * seq_len, self.n_embd))
         return self.lm_head(h).view(batch_size, seq_len, self.n_vocab)
 
-    def new_cache(self, batch_size: int):
-        """A KVCache for this model and a batch of batch_size rows."""
+    def new_cache(self, batch_size: int, kv_dtype=None):
+        """A KVCache for this model and a batch of batch_size rows. kv_dtype: None / "fp32", or
+        "bf16" / "fp8" for a quantised cache (KVCache)."""
         from .kv_cache import KVCache
         return KVCache(self.n_layer, batch_size, self.n_head, self.n_positions, self.n_embd // self.n_head,
-                       self.backend, n_kv_head=self.n_kv_head)
+                       self.backend, n_kv_head=self.n_kv_head, kv_dtype=kv_dtype)
 
     def _forward_cached(self, idx, kv_len, cache):
         if not self.use_flash_attention:
@@ -434,7 +451,7 @@ class DecoderLM(Module):
 
     def generate(self, prompts, max_new_tokens: int, eos_id=None, use_cache: bool = True,
                  temperature: float = 0.0, top_k: int = 0, seed=None, graph: bool = False, sync_every: int = 8,
-                 prefill_chunk=None):
+                 prefill_chunk=None, kv_dtype=None):
         """Decoding of a list of token-id lists, as the reference's generate
         (project/run_machine_translation.py:271-328); returns the new ids per prompt (without
         the eos that stopped a row). A row also stops once it holds more than n_positions tokens.
@@ -467,7 +484,13 @@ class DecoderLM(Module):
         a time, the first chunk into the empty cache and the others as extend steps on it
         (Tensor.flash_attention_extend), so the prefill's activations, the [B, C, V] logits among
         them, are bounded by C instead of the longest prompt. The tokens are those of
-        prefill_chunk=None; a sampled draw still depends on (seed, b) alone."""
+        prefill_chunk=None; a sampled draw still depends on (seed, b) alone.
+
+        kv_dtype="bf16" / "fp8" (needs use_cache=True): the KV cache is stored quantised (KVCache);
+        None / "fp32" is the fp32 cache. The prompt's own attention runs on the fresh fp32 K / V,
+        every later step reads the quantised rows, so the ids may differ from the fp32 cache's.
+        With prefill_chunk the later chunks already see the quantised prefix, so the ids may also
+        differ from those of the one-shot prefill."""
         prompts = [[int(t) for t in p] for p in prompts]
         if not prompts or any(len(p) == 0 for p in prompts):
             raise ValueError("generate needs at least one prompt and no empty prompt")
@@ -477,6 +500,13 @@ class DecoderLM(Module):
         temperature = float(temperature)
         if not temperature >= 0.0:
             raise ValueError(f"temperature must be >= 0, got {temperature}")
+        if kv_dtype == "fp32":
+            kv_dtype = None
+        if kv_dtype is not None:
+            if kv_dtype not in ("bf16", "fp8"):
+                raise ValueError(f'kv_dtype must be None, "fp32", "bf16" or "fp8", got {kv_dtype!r}')
+            if not use_cache:
+                raise ValueError("generate(kv_dtype=...) stores a quantised KV cache: it needs use_cache=True")
         if graph and not use_cache:
             raise ValueError("generate(graph=True) replays the cached decode step: it needs use_cache=True")
         if prefill_chunk is not None:
@@ -500,11 +530,11 @@ class DecoderLM(Module):
         try:
             if graph:
                 return self._generate_graph(prompts, max_new_tokens, eos_id, sampler, max(1, int(sync_every)),
-                                            prefill_chunk)
+                                            prefill_chunk, kv_dtype)
             if temperature == 0.0:
                 sampler = None
             if use_cache:
-                return self._generate_cached(prompts, max_new_tokens, eos_id, sampler, prefill_chunk)
+                return self._generate_cached(prompts, max_new_tokens, eos_id, sampler, prefill_chunk, kv_dtype)
             return [self._generate_plain(p, max_new_tokens, eos_id, sampler) for p in prompts]
         finally:
             if was_training:
@@ -526,11 +556,11 @@ class DecoderLM(Module):
             new.append(nxt)
         return new
 
-    def _generate_cached(self, prompts, max_new_tokens, eos_id, sampler=None, prefill_chunk=None):
+    def _generate_cached(self, prompts, max_new_tokens, eos_id, sampler=None, prefill_chunk=None, kv_dtype=None):
         B = len(prompts)
         lens = np.array([len(p) for p in prompts], dtype=np.int64)
         T = int(lens.max())
-        cache = self.new_cache(B)
+        cache = self.new_cache(B, kv_dtype)
         idx = np.zeros((B, T), dtype=datatype)
         for b, p in enumerate(prompts):
             idx[b, :len(p)] = p
@@ -600,7 +630,8 @@ class DecoderLM(Module):
         next such call captures again)."""
         self.__dict__.pop("_decode_graphs", None)
 
-    def _generate_graph(self, prompts, max_new_tokens, eos_id, sampler, sync_every, prefill_chunk=None):
+    def _generate_graph(self, prompts, max_new_tokens, eos_id, sampler, sync_every, prefill_chunk=None,
+                        kv_dtype=None):
         from .graphs import StepGraph
         if not self.use_flash_attention:
             raise ValueError("a KV cache needs use_flash_attention=True")
@@ -611,14 +642,15 @@ class DecoderLM(Module):
             return new
         temperature, top_k, seed = sampler
         graphs = self.__dict__.setdefault("_decode_graphs", {})
-        entry = graphs.pop(B, None)
+        slot = B if kv_dtype is None else (B, kv_dtype)  # a quantised cache has buffers and graphs of its own
+        entry = graphs.pop(slot, None)
         if entry is None:
             # per batch size: the buffers (one KVCache) and the graphs captured over them; the
             # last MAX_DECODE_BATCH_SIZES batch sizes are kept
             while len(graphs) >= self.MAX_DECODE_BATCH_SIZES:
                 graphs.pop(next(iter(graphs)))
-            entry = {"state": _DecodeState(self, B), "graphs": {}}
-        graphs[B] = entry  # most recently used last
+            entry = {"state": _DecodeState(self, B, kv_dtype), "graphs": {}}
+        graphs[slot] = entry  # most recently used last
         st = entry["state"]
         st.begin(temperature, top_k, eos_id, seed)
         # eager: the prefill (the prompt length varies) and the first token
@@ -683,11 +715,11 @@ class _DecodeState:
     flags, the token history [B, n_positions] (no row returns more tokens than that), the step
     counter and the seed slot."""
 
-    def __init__(self, lm: DecoderLM, batch_size: int):
+    def __init__(self, lm: DecoderLM, batch_size: int, kv_dtype=None):
         import torch
         from .tensor import Tensor
         from .tensor_data import TensorData
-        self.cache = lm.new_cache(batch_size)
+        self.cache = lm.new_cache(batch_size, kv_dtype)
         self.ids_dev = torch.zeros(batch_size, dtype=torch.float32, device="cuda")
         self.ids = Tensor(TensorData(self.ids_dev, (batch_size, 1)), backend=lm.backend)
         self.ids_i32 = torch.zeros(batch_size, dtype=torch.int32, device="cuda")

@@ -132,5 +132,9 @@ class TensorBackend:
         self.flash_attention_decode = getattr(ops, "flash_attention_decode", None)
         self.flash_attention_extend = getattr(ops, "flash_attention_extend", None)
         self.kv_cache_append = getattr(ops, "kv_cache_append", None)
+        # quantised KV cache (optional: KVCache(kv_dtype=...) needs them)
+        self.kv_cache_append_quant = getattr(ops, "kv_cache_append_quant", None)
+        self.flash_attention_decode_kvq = getattr(ops, "flash_attention_decode_kvq", None)
+        self.kv_cache_dequant = getattr(ops, "kv_cache_dequant", None)
         # the next token chosen on the device (optional: a backend without it keeps the host argmax)
         self.select_token = getattr(ops, "select_token", None)

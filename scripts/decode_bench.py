@@ -47,6 +47,19 @@ dtype), 512 new tokens on a cached prefix of n - 512, alternated in one process 
             for the prefill of an empty cache, the same arithmetic), against that one-shot forward
 
 The script exits non-zero unless the extend step is faster than the full forward at every row.
+
+--kvq-legs instead writes profiles/decode_kvq_bench.json: per shape of KVQ_SHAPES and Hkv in {H, H/4},
+Nq = 1, fp32 queries and O in every leg, alternated in one process and swapping places each round:
+
+  fp32      one mt_flash_attn_decode_gqa step (MT_F32) on fp32 caches: what DecoderLM pays without kv_dtype
+  bf16      one mt_flash_attn_decode_kvq step on bf16 caches
+  fp8       one mt_flash_attn_decode_kvq step on e4m3 caches with their row scales
+  copy_*    a device-to-device copy of each leg's own K / V (and scale) bytes
+
+and the append kernels alone for a 1-token step (mt_kv_cache_append fp32, mt_kv_cache_append_quant).
+Each leg rotates over enough cache copies of its own to exceed twice the Infinity Cache. The script
+exits non-zero unless, with Hkv = H, each quantised step is faster than the fp32 step of the same
+run by more than the 4 % box-to-box variation (t_quant * 1.04 < t_fp32).
 """
 import argparse
 import json
@@ -320,6 +333,142 @@ def extend_legs(args, torch, _hip):
         raise SystemExit(f"the extend step is not faster than the full causal forward at {slower}")
 
 
+KVQ_SHAPES = [(8, 16, 4096, 64), (1, 16, 16384, 128)]
+
+
+def bench_kvq(torch, _hip, B, H, L, d, rounds, warmup):
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rnd = lambda *s: torch.randn(*s, generator=g, device="cuda", dtype=torch.float32)  # noqa: E731
+    q = rnd(B, 1, H, d).permute(0, 2, 1, 3)
+    kvl = torch.full((B,), L, dtype=torch.int32, device="cuda")
+    zero = torch.zeros(B, dtype=torch.int32, device="cuda")
+    o = torch.empty((B, 1, H, d), dtype=torch.float32, device="cuda").permute(0, 2, 1, 3)
+    m, l = (torch.empty((B, H, 1), dtype=torch.float32, device="cuda") for _ in range(2))
+    kinds = {"fp32": (torch.float32, 4, None), "bf16": (torch.bfloat16, 2, _hip.MT_KV_BF16),
+             "fp8": (torch.uint8, 1, _hip.MT_KV_FP8)}
+    rows = []
+    for Hkv in (H, H // 4):
+        src = (rnd(B, L, Hkv, d).permute(0, 2, 1, 3), rnd(B, L, Hkv, d).permute(0, 2, 1, 3))
+        legs, info = {}, {}
+        for name, (dt, es, code) in kinds.items():
+            kv_bytes = 2 * B * Hkv * L * d * es + (2 * B * Hkv * L * 4 if name == "fp8" else 0)
+            nset = min(72, max(2, -(-2 * ICACHE // kv_bytes) + 1))
+            sets = []
+            for _ in range(nset):  # every set holds the same values in buffers of its own
+                kc, vc = (torch.empty((B, L, Hkv, d), dtype=dt, device="cuda").permute(0, 2, 1, 3) for _ in range(2))
+                ks = vs = None
+                if name == "fp8":
+                    ks, vs = (torch.empty((B, Hkv, L), dtype=torch.float32, device="cuda") for _ in range(2))
+                if code is None:
+                    kc.copy_(src[0])
+                    vc.copy_(src[1])
+                else:
+                    _hip.kv_cache_append_quant(src[0], src[1], kc, vc, zero, ks, vs)
+                sets.append((kc, vc, ks, vs))
+            if code is None:
+                nsplit, span, tile = _hip.decode_splits(0, B, H, 1, L, d, Hkv=Hkv)
+                ws_bytes = _hip.decode_workspace_bytes(0, B, H, 1, L, d, Hkv=Hkv)
+            else:
+                nsplit, span, tile = _hip.decode_kvq_splits(code, B, H, 1, L, d, Hkv=Hkv)
+                ws_bytes = _hip.decode_kvq_workspace_bytes(code, B, H, 1, L, d, Hkv=Hkv)
+            ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device="cuda")
+            dst = tuple(None if t is None else torch.empty_like(t) for t in sets[0])
+
+            def step(i, sets=sets, nset=nset, ws=ws, quant=code is not None):
+                kc, vc, ks, vs = sets[i % nset]
+                if quant:
+                    _hip.flash_decode_kvq(q, kc, vc, ks, vs, kv_len=kvl, causal=True, out=o, m=m, l=l, workspace=ws)
+                else:
+                    _hip.flash_decode(q, kc, vc, kv_len=kvl, causal=True, out=o, m=m, l=l, workspace=ws)
+
+            def copy(i, sets=sets, nset=nset, dst=dst):
+                for a, b in zip(dst, sets[i % nset]):
+                    if a is not None:
+                        a.copy_(b)
+            legs[name] = (step, nset * -(-24 // nset))   # whole turns over the leg's cache sets
+            legs["copy_" + name] = (copy, nset)
+            info[name] = dict(kv_bytes=kv_bytes, nset=nset, splits=nsplit, span=span, tile=tile, ws_bytes=ws_bytes,
+                              alg=kv_bytes + 2 * B * H * d * 4 + 2 * ws_bytes)
+        for fn, inner in legs.values():
+            for _ in range(warmup):
+                _timed(torch, fn, inner)
+        times = {k: [] for k in legs}
+        steps = ["fp32", "bf16", "fp8"]
+        for r in range(rounds):  # the legs alternate inside every round, the decode legs swapping places
+            order = steps[r % 3:] + steps[:r % 3] + ["copy_" + k for k in steps]
+            for k in order:
+                fn, inner = legs[k]
+                times[k].append(_timed(torch, fn, inner))
+        med = {k: statistics.median(v) for k, v in times.items()}
+        G = H // Hkv
+        row = {"shape": [B, H, L, d], "nq": 1, "kv_heads": Hkv, "group": G, "rounds": rounds}
+        for k in steps:
+            i = info[k]
+            row.update({
+                f"{k}_s_median": med[k], f"{k}_s_min": min(times[k]), f"{k}_s_max": max(times[k]),
+                f"{k}_copy_s_median": med["copy_" + k], f"{k}_kv_bytes": i["kv_bytes"],
+                f"{k}_algorithmic_bytes": i["alg"], f"{k}_bytes_per_s": i["alg"] / med[k],
+                f"{k}_copy_read_bytes_per_s": i["kv_bytes"] / med["copy_" + k],
+                f"{k}_splits": i["splits"], f"{k}_span_keys": i["span"], f"{k}_tile_keys": i["tile"],
+                f"{k}_workspace_bytes": i["ws_bytes"], f"{k}_cache_sets_rotated": i["nset"],
+                f"{k}_launches_per_timing": legs[k][1]})
+        for k in ("bf16", "fp8"):
+            row[f"{k}_over_fp32_time"] = med[k] / med["fp32"]
+            row[f"{k}_over_fp32_bytes"] = info[k]["kv_bytes"] / info["fp32"]["kv_bytes"]
+            # the one condition (gated at Hkv = H): faster than the fp32-cache step by more than the 4 %
+            # box-to-box variation
+            row[f"{k}_faster_than_fp32"] = bool(med[k] * 1.04 < med["fp32"])
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del legs, src
+        torch.cuda.empty_cache()
+    return rows
+
+
+def bench_kvq_append(torch, _hip, B, H, L, d, rounds, warmup, inner=64):
+    """The append kernels alone for a 1-token step on caches of L rows."""
+    g = torch.Generator(device="cuda").manual_seed(0)
+    kn, vn = (torch.randn(B, 1, H, d, generator=g, device="cuda").permute(0, 2, 1, 3) for _ in range(2))
+    pos = torch.full((B,), L - 1, dtype=torch.int32, device="cuda")
+    legs = {}
+    for name, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16), ("fp8", torch.uint8)):
+        kc, vc = (torch.zeros((B, L, H, d), dtype=dt, device="cuda").permute(0, 2, 1, 3) for _ in range(2))
+        ks = vs = None
+        if name == "fp8":
+            ks, vs = (torch.zeros((B, H, L), dtype=torch.float32, device="cuda") for _ in range(2))
+        if name == "fp32":
+            legs[name] = lambda i, kc=kc, vc=vc: _hip.kv_cache_append(kn, vn, kc, vc, pos)
+        else:
+            legs[name] = lambda i, kc=kc, vc=vc, ks=ks, vs=vs: _hip.kv_cache_append_quant(kn, vn, kc, vc, pos, ks, vs)
+    for fn in legs.values():
+        for _ in range(warmup):
+            _timed(torch, fn, inner)
+    times = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():
+            times[k].append(_timed(torch, fn, inner))
+    return {"shape": [B, H, L, d], "new_tokens": 1, "rounds": rounds, "launches_per_timing": inner,
+            **{f"append_{k}_s_median": statistics.median(v) for k, v in times.items()},
+            **{f"append_{k}_s_min": min(v) for k, v in times.items()}}
+
+
+def kvq_legs(args, torch, _hip):
+    res = {"device": torch.cuda.get_device_name(0), "kernels": [], "append": []}
+    for B, H, L, d in KVQ_SHAPES:
+        res["kernels"] += bench_kvq(torch, _hip, B, H, L, d, args.rounds, args.warmup)
+        r = bench_kvq_append(torch, _hip, B, H, L, d, args.rounds, args.warmup)
+        print(json.dumps(r), flush=True)
+        res["append"].append(r)
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(args.kvq_out), exist_ok=True)
+    with open(args.kvq_out, "w") as f:
+        json.dump(res, f, indent=1)
+    slow = [(r["shape"], k, round(r[f"{k}_over_fp32_time"], 3)) for r in res["kernels"] if r["group"] == 1
+            for k in ("bf16", "fp8") if not r[f"{k}_faster_than_fp32"]]
+    if slow:
+        raise SystemExit(f"a quantised-cache step is not faster than the fp32-cache step by more than 4 % at {slow}")
+
+
 def bench_generate(minitorch, n_positions, prompt_len, new_tokens, batch, rounds):
     np.random.seed(0)
     backend = minitorch.TensorBackend(minitorch.HipKernelOps)
@@ -426,6 +575,9 @@ def main():
     ap.add_argument("--extend-legs", action="store_true",
                     help="run the extend-attention legs instead, into --extend-out")
     ap.add_argument("--extend-out", default=os.path.join(ROOT, "profiles", "extend_bench.json"))
+    ap.add_argument("--kvq-legs", action="store_true",
+                    help="run the quantised-KV-cache decode legs instead, into --kvq-out")
+    ap.add_argument("--kvq-out", default=os.path.join(ROOT, "profiles", "decode_kvq_bench.json"))
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--skip-generate", action="store_true")
@@ -441,6 +593,8 @@ def main():
         return gqa_legs(args, torch, _hip)
     if args.extend_legs:
         return extend_legs(args, torch, _hip)
+    if args.kvq_legs:
+        return kvq_legs(args, torch, _hip)
     res = {"device": torch.cuda.get_device_name(0), "kernels": [], "generate": []}
     for B, H, L, d, name in SHAPES:
         r = bench_shape(torch, _hip, B, H, L, d, name, args.rounds, args.warmup)
