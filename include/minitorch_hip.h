@@ -260,6 +260,65 @@ int mt_kv_cache_dequant(int kv_dtype, const void* k_cache, const void* v_cache, 
                         int64_t d, const int64_t* kcache_strides, const int64_t* vcache_strides,
                         const int64_t* kout_strides, const int64_t* vout_strides, const int* kv_len, void* stream);
 
+/* ---- paged KV cache ----------------------------------------------------------
+ * K and V rows live in pages of P rows (P a power of two >= 16) taken from a pool, per layer and
+ * per K / V:
+ *   k_pool, v_pool:  [n_pages, Hkv, P, d] through strides (page, head, row) in elements,
+ *                    NULL = contiguous; unit-stride d, 16-B rows as decode defines them
+ *   block_table:     device int32 [B, W], dense. Logical key j of batch row b is row j % P of
+ *                    page block_table[b][j / P]; the logical capacity is Nk = W * P. A negative
+ *                    entry is an unallocated page.
+ * Refused with a status and a mt_last_error() message before any device call: P not a power of
+ * two or below 16, W <= 0, n_pages <= 0, a NULL block_table, and whatever
+ * mt_flash_attn_decode_gqa (decode) or mt_kv_cache_append (append, gather) refuses: Nq outside
+ * 1..8, Hkv not dividing H, d > 256, rows not 16-B aligned, a short workspace.
+ *
+ * mt_flash_attn_decode_paged: mt_flash_attn_decode_gqa's contract (dtypes, 1 <= Nq <= 8,
+ * bottom-right causal alignment, row packing, (0, -inf, 0) for a query with no visible key, two
+ * plain launches, fixed-order combine, the same workspace layout) on a paged cache. The plan
+ * (splits, span, tile, packing, workspace bytes) is the one mt_flash_attn_decode_gqa_splits gives
+ * at Nk = W * P: a function of the sizes only, never of kv_len or of the table's contents, so a
+ * captured launch replays as the cache fills. The arithmetic and its order are the plain
+ * kernel's: O, m and l have the bits mt_flash_attn_decode_gqa gives on a contiguous cache that
+ * holds the same rows. With n = clamp(kv_len[b], 0, W * P), no table entry at index
+ * >= ceil(n / P) is read and no pool row of a key >= n; every table entry below that must be a
+ * page of the pool. Decode does NOT detect an entry that is not: an entry outside [0, n_pages),
+ * a negative (unallocated) one included, is clamped into the range (a negative one reads the last
+ * page), so its rows enter the softmax as valid keys: a silently wrong result, never an address
+ * outside the pool. (Append and gather drop such rows instead.) The caller keeps the entries
+ * below ceil(n / P) allocated.
+ *
+ * mt_kv_cache_append_paged: writes the new rows k_new / v_new ([B, Hkv, Nq, d], any 16-B-row
+ * strides) to the logical rows pos[b] .. pos[b] + cnt - 1 of batch row b, cnt =
+ * clamp(count[b], 0, Nq) (pos, count: device int32 [B]; count NULL = Nq). Dropped: rows past cnt,
+ * logical rows outside [0, W * P), rows whose table entry is negative (or >= n_pages). Nothing
+ * else in the pools is written. dtype: MT_F32 or MT_BF16 (MT_BF16_F32OUT is taken as MT_BF16).
+ *
+ * mt_kv_cache_gather_paged: writes the rows j < clamp(kv_len[b], 0, W * P) (kv_len NULL: W * P) of
+ * the contiguous k_out / v_out ([B, Hkv, W * P, d] through strides in elements, 16-B rows) from
+ * the pools. Rows at or past that count are neither read nor written (and no table entry at
+ * index >= ceil(n / P) is read). */
+int mt_flash_attn_decode_paged_splits(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t W,
+                                      int64_t P, int64_t d, int64_t* span_keys, int64_t* tile_keys);
+int64_t mt_flash_attn_decode_paged_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq,
+                                                   int64_t W, int64_t P, int64_t d);
+int mt_flash_attn_decode_paged(int dtype, int causal, const void* q, const void* k_pool, const void* v_pool,
+                               void* o, float* m, float* l, int64_t B, int64_t H, int64_t Hkv, int64_t Nq,
+                               int64_t W, int64_t P, int64_t n_pages, int64_t d, const int64_t* q_strides,
+                               const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides,
+                               const int* block_table, const int* kv_len,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+int mt_kv_cache_append_paged(int dtype, const void* k_new, const void* v_new, void* k_pool, void* v_pool,
+                             int64_t B, int64_t Hkv, int64_t Nq, int64_t W, int64_t P, int64_t n_pages, int64_t d,
+                             const int64_t* knew_strides, const int64_t* vnew_strides,
+                             const int64_t* kpool_strides, const int64_t* vpool_strides,
+                             const int* block_table, const int* pos, const int* count, void* stream);
+int mt_kv_cache_gather_paged(int dtype, const void* k_pool, const void* v_pool, void* k_out, void* v_out,
+                             int64_t B, int64_t Hkv, int64_t W, int64_t P, int64_t n_pages, int64_t d,
+                             const int64_t* kpool_strides, const int64_t* vpool_strides,
+                             const int64_t* kout_strides, const int64_t* vout_strides,
+                             const int* block_table, const int* kv_len, void* stream);
+
 /* ---- generation: the next token chosen on the device ------------------------
  * One id per row of the fp32 logits [B, V] (rows row_stride >= V elements apart, unit-stride
  * columns; what lies between the rows is never read). Stream-ordered, allocates nothing, does

@@ -10,7 +10,7 @@
 
 namespace mt {
 // dtype, sizes and the 16-B row rule on d; 0 or the error status
-static int decode_sizes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d) {
+int decode_sizes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d) {
   if (dtype != MT_F32 && dtype != MT_BF16 && dtype != MT_BF16_F32OUT)
     return set_error("unsupported dtype %d", dtype);
   if (B <= 0 || H <= 0 || Nk <= 0 || d <= 0)
@@ -52,7 +52,7 @@ static int extend_sizes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq
   return 0;
 }
 
-static void strides_or_dense(int64_t dst[3], const int64_t* src, int64_t H, int64_t N, int64_t d) {
+void strides_or_dense(int64_t dst[3], const int64_t* src, int64_t H, int64_t N, int64_t d) {
   if (src) {
     dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
   } else {
@@ -60,7 +60,7 @@ static void strides_or_dense(int64_t dst[3], const int64_t* src, int64_t H, int6
   }
 }
 
-static int aligned16(const char* what, const void* p, const int64_t s[3], int esize) {
+int aligned16(const char* what, const void* p, const int64_t s[3], int esize) {
   const int64_t epc = 16 / esize;
   if (!p) return set_error("%s is NULL", what);
   if ((uintptr_t)p & 15) return set_error("%s is not 16-B aligned", what);
@@ -69,7 +69,7 @@ static int aligned16(const char* what, const void* p, const int64_t s[3], int es
   return 0;
 }
 
-static int64_t decode_ws_bytes(const DecodePlan& p, int64_t B, int64_t H, int64_t Nq, int64_t d) {
+int64_t decode_ws_bytes(const DecodePlan& p, int64_t B, int64_t H, int64_t Nq, int64_t d) {
   return p.nsplit == 1 ? 0 : B * H * Nq * p.nsplit * (d + 2) * 4;
 }
 }  // namespace mt

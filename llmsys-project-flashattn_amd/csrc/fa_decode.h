@@ -1,5 +1,6 @@
-// Shared between fa_decode.hip (kernels, launchers), fa_kvq.hip (the quantised-cache kernels, which
-// reuse the lane-group helpers and the combine pass) and capi_decode.hip / capi_kvq.hip (the C ABI).
+// Shared between fa_decode.hip (kernels, launchers), fa_kvq.hip and fa_paged.hip (the quantised-cache
+// and paged-cache kernels, which reuse the lane-group helpers and the combine pass) and capi_decode.hip
+// / capi_kvq.hip / capi_paged.hip (the C ABI).
 #pragma once
 #include "fa_common.h"
 
@@ -34,6 +35,12 @@ hipError_t launch_decode_combine(const DecodeArgs& a, int64_t B, hipStream_t st)
 hipError_t launch_kv_append(const AppendArgs& a, hipStream_t st);
 int set_error(const char* fmt, ...);           // capi_flash.hip
 int check_hip(hipError_t e, const char* where);
+// argument checks of the decode C ABI (capi_decode.hip; capi_paged.hip applies them at Nk = W * P):
+// 0, or the error status with the message set
+int decode_sizes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d);
+void strides_or_dense(int64_t dst[3], const int64_t* src, int64_t H, int64_t N, int64_t d);
+int aligned16(const char* what, const void* p, const int64_t s[3], int esize);
+int64_t decode_ws_bytes(const DecodePlan& p, int64_t B, int64_t H, int64_t Nq, int64_t d);
 
 constexpr int kDecWaves = 4;    // waves per workgroup
 constexpr int kDecUnroll = 4;   // key loads of K (and of V) in flight per wave and step
@@ -64,5 +71,37 @@ template <int LPK> __device__ __forceinline__ float group_sum(float v) {
 }
 
 __device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
+
+// a 16-B chunk of a Q / K / V row widened to fp32 (fa_decode.hip, fa_paged.hip)
+template <typename T> struct Chunk;
+template <> struct Chunk<float> {
+  static constexpr int N = 4;
+  static __device__ __forceinline__ void unpack(const uint4& u, float* f) {
+    f[0] = __builtin_bit_cast(float, u.x); f[1] = __builtin_bit_cast(float, u.y);
+    f[2] = __builtin_bit_cast(float, u.z); f[3] = __builtin_bit_cast(float, u.w);
+  }
+};
+template <> struct Chunk<bf16> {
+  static constexpr int N = 8;
+  static __device__ __forceinline__ void unpack(const uint4& u, float* f) {
+    const unsigned w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      f[2 * i] = __builtin_bit_cast(float, w[i] << 16);
+      f[2 * i + 1] = __builtin_bit_cast(float, w[i] & 0xffff0000u);
+    }
+  }
+};
+
+// 4 consecutive O elements of one row: fp32 (16-B store) or bf16 (8-B store)
+__device__ __forceinline__ void store_o4(void* o, int o_f32, int64_t e, const float4& x) {
+  if (o_f32) {
+    *(float4*)((float*)o + e) = x;
+  } else {
+    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+    bf16x4 r = {(bf16)x.x, (bf16)x.y, (bf16)x.z, (bf16)x.w};
+    *(bf16x4*)((bf16*)o + e) = r;
+  }
+}
 
 }  // namespace mt

@@ -72,37 +72,6 @@ DecodePlan decode_plan(int esize, int64_t B, int64_t H, int64_t Hkv, int64_t Nq,
   return p;
 }
 
-template <typename T> struct Chunk;
-template <> struct Chunk<float> {
-  static constexpr int N = 4;
-  static __device__ __forceinline__ void unpack(const uint4& u, float* f) {
-    f[0] = __builtin_bit_cast(float, u.x); f[1] = __builtin_bit_cast(float, u.y);
-    f[2] = __builtin_bit_cast(float, u.z); f[3] = __builtin_bit_cast(float, u.w);
-  }
-};
-template <> struct Chunk<bf16> {
-  static constexpr int N = 8;
-  static __device__ __forceinline__ void unpack(const uint4& u, float* f) {
-    const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f[2 * i] = __builtin_bit_cast(float, w[i] << 16);
-      f[2 * i + 1] = __builtin_bit_cast(float, w[i] & 0xffff0000u);
-    }
-  }
-};
-
-// 4 consecutive O elements of one row: fp32 (16-B store) or bf16 (8-B store)
-__device__ __forceinline__ void store_o4(void* o, int o_f32, int64_t e, const float4& x) {
-  if (o_f32) {
-    *(float4*)((float*)o + e) = x;
-  } else {
-    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-    bf16x4 r = {(bf16)x.x, (bf16)x.y, (bf16)x.z, (bf16)x.w};
-    *(bf16x4*)((bf16*)o + e) = r;
-  }
-}
-
 // fp32, one row, d <= 64 sits at the 96-VGPR edge of 5 waves per SIMD: ask for them (the allocator
 // otherwise lands on 95-98 from one build to the next)
 template <typename T, int LPK, int NQ>

@@ -76,6 +76,14 @@ _PROTOS = {
                                         _i64p, _i64p, _i64p, _i64p, _vp, _vp]),
     "mt_kv_cache_dequant": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64,
                                    _i64p, _i64p, _i64p, _i64p, _vp, _vp]),
+    "mt_flash_attn_decode_paged_splits": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64p, _i64p]),
+    "mt_flash_attn_decode_paged_workspace_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64]),
+    "mt_flash_attn_decode_paged": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                          _i64, _i64, _i64, _i64p, _i64p, _i64p, _i64p, _vp, _vp, _vp, _i64, _vp]),
+    "mt_kv_cache_append_paged": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                        _i64p, _i64p, _i64p, _i64p, _vp, _vp, _vp, _vp]),
+    "mt_kv_cache_gather_paged": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
+                                        _i64p, _i64p, _i64p, _i64p, _vp, _vp, _vp]),
     "mt_select_token": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _i64, ctypes.c_uint64, _vp, _i64,
                                _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "mt_attn_softmax_fw": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64p, _int, _vp]),
@@ -605,6 +613,128 @@ def kv_cache_dequant(k_cache, v_cache, k_scale=None, v_scale=None, kv_len=None, 
         code, k_cache.data_ptr(), v_cache.data_ptr(), ksp, vsp, k_out.data_ptr(), v_out.data_ptr(),
         B, Hkv, Nk, d, strides3(k_cache), strides3(v_cache), strides3(k_out), strides3(v_out),
         None if kv is None else kv.data_ptr(), st), "mt_kv_cache_dequant")
+    return k_out, v_out
+
+
+# ---- paged KV cache (mt_flash_attn_decode_paged / mt_kv_cache_append_paged / mt_kv_cache_gather_paged) ----
+def _paged_pools(name, k_pool, v_pool, block_table, B):
+    """Checks shared by the three entry points; returns (n_pages, Hkv, P, d, W). The pools are
+    [n_pages,Hkv,P,d] views (any strides with unit-stride d), the table a dense device int32 [B,W]."""
+    torch = _torch()
+    _check_dev(k_pool, v_pool, block_table)
+    if k_pool.dim() != 4 or v_pool.shape != k_pool.shape or v_pool.dtype != k_pool.dtype:
+        raise ValueError(f"{name}: the pools must be two [n_pages,Hkv,P,d] tensors of one dtype")
+    if block_table.dtype != torch.int32 or block_table.dim() != 2 or not block_table.is_contiguous():
+        raise ValueError(f"{name}: the block table must be a contiguous device int32 [B,W] tensor")
+    if block_table.shape[0] != B:
+        raise ValueError(f"{name}: the block table has {block_table.shape[0]} rows, the batch {B}")
+    n_pages, Hkv, P, d = k_pool.shape
+    return n_pages, Hkv, P, d, block_table.shape[1]
+
+
+def decode_paged_splits(dtype: int, B: int, H: int, Nq: int, W: int, P: int, d: int, Hkv: Optional[int] = None):
+    """(splits, span_keys, tile_keys) of mt_flash_attn_decode_paged: decode_splits' answer at
+    Nk = W * P. A function of the sizes only."""
+    span, tile = ctypes.c_int64(0), ctypes.c_int64(0)
+    n = lib().mt_flash_attn_decode_paged_splits(dtype, B, H, H if Hkv is None else Hkv, Nq, W, P, d,
+                                                ctypes.byref(span), ctypes.byref(tile))
+    if n <= 0:
+        raise ValueError(lib().mt_last_error().decode(errors="replace"))
+    return n, span.value, tile.value
+
+
+def decode_paged_workspace_bytes(dtype: int, B: int, H: int, Nq: int, W: int, P: int, d: int,
+                                 Hkv: Optional[int] = None) -> int:
+    n = lib().mt_flash_attn_decode_paged_workspace_bytes(dtype, B, H, H if Hkv is None else Hkv, Nq, W, P, d)
+    if n < 0:
+        raise ValueError(lib().mt_last_error().decode(errors="replace"))
+    return int(n)
+
+
+def flash_decode_paged(q, k_pool, v_pool, block_table, kv_len=None, causal: bool = True, out=None, m=None,
+                       l=None, workspace=None, out_dtype=None, stream: Optional[int] = None):
+    """Decode attention on a paged cache (mt_flash_attn_decode_paged): flash_decode's contract with
+    q [B,H,Nq,d] against the page pools [n_pages,Hkv,P,d] (any strides with unit-stride d) through
+    block_table (device int32 [B,W]: key j of row b is row j % P of page block_table[b, j // P]).
+    The first kv_len[b] of the W * P logical keys are visible (None: all). Returns (O, m, l).
+    workspace: a device buffer of at least decode_paged_workspace_bytes (allocated when None)."""
+    torch = _torch()
+    _check_dev(q)
+    B, H, Nq, d = q.shape
+    n_pages, Hkv, P, dp, W = _paged_pools("flash_decode_paged", k_pool, v_pool, block_table, B)
+    if dp != d:
+        raise ValueError(f"pool shape {tuple(k_pool.shape)} does not match q {tuple(q.shape)}")
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"the pools' {Hkv} heads do not divide q's {H} heads")
+    if not (q.dtype == k_pool.dtype == v_pool.dtype):
+        raise TypeError("q/k_pool/v_pool dtypes differ")
+    code = _decode_code(q, out, out_dtype)
+    if out is None:
+        out = torch.empty((B, H, Nq, d), dtype=torch.float32 if code == 2 else q.dtype, device=q.device)
+    if m is None:
+        m = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    if l is None:
+        l = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    need = lib().mt_flash_attn_decode_paged_workspace_bytes(code, B, H, Hkv, Nq, W, P, d)
+    if workspace is None and need > 0:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=q.device)
+    kv = _kv_arg(kv_len, B, q.device)
+    st = stream_ptr(q.device) if stream is None else stream
+    check(lib().mt_flash_attn_decode_paged(
+        code, int(causal), q.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), out.data_ptr(),
+        m.data_ptr(), l.data_ptr(), B, H, Hkv, Nq, W, P, n_pages, d, strides3(q), strides3(k_pool),
+        strides3(v_pool), strides3(out), block_table.data_ptr(), None if kv is None else kv.data_ptr(),
+        None if workspace is None else workspace.data_ptr(),
+        0 if workspace is None else workspace.numel() * workspace.element_size(), st),
+        "mt_flash_attn_decode_paged")
+    return out, m, l
+
+
+def kv_cache_append_paged(k_new, v_new, k_pool, v_pool, block_table, pos, count=None,
+                          stream: Optional[int] = None) -> None:
+    """Copy the new rows k_new / v_new [B,Hkv,Nq,d] into the page pools [n_pages,Hkv,P,d] at the
+    logical rows pos[b] .. pos[b] + count[b] - 1 of batch row b (pos, count: [B] int32 on the
+    device; count None: Nq). Rows past the count, past W * P or in an unallocated page (a negative
+    table entry) are dropped."""
+    _check_dev(k_new, v_new)
+    B, Hkv, Nq, d = k_new.shape
+    n_pages, Hp, P, dp, W = _paged_pools("kv_cache_append_paged", k_pool, v_pool, block_table, B)
+    if v_new.shape != k_new.shape or (Hp, dp) != (Hkv, d):
+        raise ValueError("kv_cache_append_paged: shapes do not match")
+    if not (k_new.dtype == v_new.dtype == k_pool.dtype):
+        raise TypeError("kv_cache_append_paged: dtypes differ")
+    p = _kv_arg(pos, B, k_new.device)
+    cnt = _kv_arg(count, B, k_new.device)
+    st = stream_ptr(k_new.device) if stream is None else stream
+    check(lib().mt_kv_cache_append_paged(
+        dtype_code(k_new), k_new.data_ptr(), v_new.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
+        B, Hkv, Nq, W, P, n_pages, d, strides3(k_new), strides3(v_new), strides3(k_pool), strides3(v_pool),
+        block_table.data_ptr(), p.data_ptr(), None if cnt is None else cnt.data_ptr(), st),
+        "mt_kv_cache_append_paged")
+
+
+def kv_cache_gather_paged(k_pool, v_pool, block_table, kv_len=None, k_out=None, v_out=None,
+                          stream: Optional[int] = None):
+    """The first kv_len[b] logical rows (None: all W * P) of every batch row of a paged cache
+    (mt_kv_cache_gather_paged) written to the contiguous k_out / v_out [B,Hkv,W*P,d] (allocated,
+    uninitialised past those rows, when None); the other rows are neither read nor written."""
+    torch = _torch()
+    B = block_table.shape[0]
+    n_pages, Hkv, P, d, W = _paged_pools("kv_cache_gather_paged", k_pool, v_pool, block_table, B)
+    Nk = W * P
+    if k_out is None:
+        k_out = torch.empty((B, Hkv, Nk, d), dtype=k_pool.dtype, device=k_pool.device)
+    if v_out is None:
+        v_out = torch.empty((B, Hkv, Nk, d), dtype=k_pool.dtype, device=k_pool.device)
+    for t in (k_out, v_out):
+        if t.dtype != k_pool.dtype or tuple(t.shape) != (B, Hkv, Nk, d):
+            raise ValueError(f"kv_cache_gather_paged: outputs must be {k_pool.dtype} [{B}, {Hkv}, {Nk}, {d}] tensors")
+    kv = _kv_arg(kv_len, B, k_pool.device)
+    st = stream_ptr(k_pool.device) if stream is None else stream
+    check(lib().mt_kv_cache_gather_paged(
+        dtype_code(k_pool), k_pool.data_ptr(), v_pool.data_ptr(), k_out.data_ptr(), v_out.data_ptr(),
+        B, Hkv, W, P, n_pages, d, strides3(k_pool), strides3(v_pool), strides3(k_out), strides3(v_out),
+        block_table.data_ptr(), None if kv is None else kv.data_ptr(), st), "mt_kv_cache_gather_paged")
     return k_out, v_out
 
 

@@ -573,6 +573,38 @@ class HipKernelOps(TensorOps):
                               kv_len=None if kv_len is None else HipKernelOps._i32(kv_len),
                               k_out=_torch_view(Kout), v_out=_torch_view(Vout))
 
+    # ---- paged KV cache: the pools ([n_pages,Hkv,P,d] views) and the block table are torch tensors ----
+    @staticmethod
+    def kv_cache_append_paged(Knew: Tensor, Vnew: Tensor, kp, vp, block_table, pos, count=None) -> None:
+        """Write the new rows Knew / Vnew [B,Hkv,Nq,d] into the page pools kp / vp at the logical
+        rows pos[b] .. pos[b] + count[b] - 1 through block_table (mt_kv_cache_append_paged; count
+        None: all Nq rows)."""
+        _hip.kv_cache_append_paged(_torch_view(Knew), _torch_view(Vnew), kp, vp, block_table,
+                                   HipKernelOps._i32(pos), None if count is None else HipKernelOps._i32(count))
+
+    @staticmethod
+    def flash_attention_decode_paged(Q: Tensor, kp, vp, block_table, kv_len=None, causal: bool = True,
+                                     workspace=None) -> Tensor:
+        """flash_attention_decode on a paged cache (mt_flash_attn_decode_paged): the page pools kp / vp
+        [n_pages,Hkv,P,d] read through block_table [B,W]. workspace: a torch fp32 buffer of
+        _hip.decode_paged_workspace_bytes (allocated when None)."""
+        import torch
+        B, H, Nq, d = Q.shape
+        so = _layout_like(Q)
+        o = torch.empty(B * H * Nq * d, dtype=torch.float32, device="cuda")
+        _hip.flash_decode_paged(_torch_view(Q), kp, vp, block_table,
+                                kv_len=None if kv_len is None else HipKernelOps._i32(kv_len), causal=causal,
+                                out=torch.as_strided(o, (B, H, Nq, d), so), workspace=workspace)
+        return _wrap(o, (B, H, Nq, d), Q.backend, so)
+
+    @staticmethod
+    def kv_cache_gather_paged(kp, vp, block_table, kv_len, Kout: Tensor, Vout: Tensor) -> None:
+        """The first kv_len[b] logical rows of a paged cache written into the contiguous tensors
+        Kout / Vout [B,Hkv,W*P,d] (mt_kv_cache_gather_paged)."""
+        _hip.kv_cache_gather_paged(kp, vp, block_table,
+                                   kv_len=None if kv_len is None else HipKernelOps._i32(kv_len),
+                                   k_out=_torch_view(Kout), v_out=_torch_view(Vout))
+
     @staticmethod
     def select_token(logits: Tensor, temperature: float = 0.0, top_k: int = 0, seed: int = 0, rows=None, **kw):
         """The next token ids chosen on the device (mt_select_token) from logits [B, V], or from

@@ -213,6 +213,8 @@ class MultiHeadAttention(Module):
         if int(kvc.length_host.max()) + seq_len > kvc.n_positions:
             raise ValueError(f"{seq_len} new tokens do not fit the KV cache ({kvc.n_positions} positions, "
                              f"{int(kvc.length_host.max())} held)")
+        if kvc.paged:
+            return self._paged_attention(q, k, v, kv_len, lkv, prefill)
         if kvc.quantised:
             # the rows are quantised as they land; a prefill still attends the fresh fp32 K / V
             q.backend.kv_cache_append_quant(k, v, lkv.k, lkv.v, kvc.length, lkv.k_scale, lkv.v_scale)
@@ -225,6 +227,28 @@ class MultiHeadAttention(Module):
                                                           kvc.visible(seq_len), True, kvc.decode_workspace(seq_len))
         else:
             result = q.flash_attention_decode(lkv.k, lkv.v, kvc.visible(seq_len))
+        result = result.permute(0, 2, 1, 3).contiguous()
+        return result.view(batch_size, seq_len, self.n_embd)
+
+    def _paged_attention(self, q, k, v, kv_len, lkv, prefill):
+        """A prefill or a decode step on a PagedKVCache: the pages are reserved from the host
+        mirror's counts, the new rows appended through the block table, and a decode step reads the
+        pages directly (mt_flash_attn_decode_paged; the workspace is the cache's, so a captured
+        step allocates nothing). A prefill attends the fresh K / V as the contiguous cache does;
+        of a right-padded prompt batch only the kv_len[b] real rows land (a paged cache has no
+        stale tail to take the padding)."""
+        kvc = lkv.cache
+        batch_size, _, seq_len, _ = q.shape
+        new_len, count = seq_len, None
+        if prefill and kv_len is not None:
+            new_len = _new_token_counts(kv_len, batch_size, seq_len)
+            count = kvc.extend_counts(new_len)[1]
+        kvc.reserve(kvc.length_host + new_len)
+        q.backend.kv_cache_append_paged(k, v, lkv.k, lkv.v, kvc.block_table, kvc.length, count)
+        if prefill:
+            return self.self_attention(q, k, v, kv_len)
+        result = q.backend.flash_attention_decode_paged(q, lkv.k, lkv.v, kvc.block_table, kvc.visible(seq_len),
+                                                        True, kvc.decode_workspace(seq_len))
         result = result.permute(0, 2, 1, 3).contiguous()
         return result.view(batch_size, seq_len, self.n_embd)
 
@@ -241,7 +265,16 @@ class MultiHeadAttention(Module):
             raise ValueError(f"the new tokens do not fit the KV cache ({kvc.n_positions} positions, "
                              f"{int(kvc.length_host.max())} held)")
         visible, q_len = kvc.extend_counts(new_len)
-        if kvc.quantised:
+        if kvc.paged:
+            # only the real rows land (count = q_len: there is no stale tail for the padding); no
+            # extend kernel reads pages: the visible rows (the new ones included) are gathered into
+            # the cache's contiguous fp32 scratch, one extra fp32 write and read of them
+            kvc.reserve(kvc.length_host + new_len)
+            q.backend.kv_cache_append_paged(k, v, lkv.k, lkv.v, kvc.block_table, kvc.length, q_len)
+            ks, vs = kvc.scratch()
+            q.backend.kv_cache_gather_paged(lkv.k, lkv.v, kvc.block_table, visible, ks, vs)
+            result = q.flash_attention_extend(ks, vs, visible, q_len)
+        elif kvc.quantised:
             # no extend kernel reads a quantised cache: the visible rows (the new ones included) are
             # dequantised into the cache's fp32 scratch, one extra fp32 write and read of them
             q.backend.kv_cache_append_quant(k, v, lkv.k, lkv.v, kvc.length, lkv.k_scale, lkv.v_scale)
@@ -361,10 +394,18 @@ class DecoderLM(Module):
         h = self.ln(h.view(batch_size * seq_len, self.n_embd))
         return self.lm_head(h).view(batch_size, seq_len, self.n_vocab)
 
-    def new_cache(self, batch_size: int, kv_dtype=None):
+    def new_cache(self, batch_size: int, kv_dtype=None, page_size=None, n_pages=None):
         """A KVCache for this model and a batch of batch_size rows. kv_dtype: None / "fp32", or
-        "bf16" / "fp8" for a quantised cache (KVCache)."""
-        from .kv_cache import KVCache
+        "bf16" / "fp8" for a quantised cache (KVCache). page_size (a power of two >= 16): a
+        PagedKVCache of that page size whose pool holds n_pages pages (None: every row can fill
+        up); fp32 pages only."""
+        from .kv_cache import KVCache, PagedKVCache
+        if page_size is not None:
+            return PagedKVCache(self.n_layer, batch_size, self.n_head, self.n_positions, self.n_embd // self.n_head,
+                                self.backend, n_kv_head=self.n_kv_head, page_size=page_size, n_pages=n_pages,
+                                kv_dtype=kv_dtype)
+        if n_pages is not None:
+            raise ValueError("new_cache(n_pages=...) needs page_size")
         return KVCache(self.n_layer, batch_size, self.n_head, self.n_positions, self.n_embd // self.n_head,
                        self.backend, n_kv_head=self.n_kv_head, kv_dtype=kv_dtype)
 
@@ -451,7 +492,7 @@ class DecoderLM(Module):
 
     def generate(self, prompts, max_new_tokens: int, eos_id=None, use_cache: bool = True,
                  temperature: float = 0.0, top_k: int = 0, seed=None, graph: bool = False, sync_every: int = 8,
-                 prefill_chunk=None, kv_dtype=None):
+                 prefill_chunk=None, kv_dtype=None, page_size=None):
         """Decoding of a list of token-id lists, as the reference's generate
         (project/run_machine_translation.py:271-328); returns the new ids per prompt (without
         the eos that stopped a row). A row also stops once it holds more than n_positions tokens.
@@ -490,7 +531,14 @@ class DecoderLM(Module):
         None / "fp32" is the fp32 cache. The prompt's own attention runs on the fresh fp32 K / V,
         every later step reads the quantised rows, so the ids may differ from the fp32 cache's.
         With prefill_chunk the later chunks already see the quantised prefix, so the ids may also
-        differ from those of the one-shot prefill."""
+        differ from those of the one-shot prefill.
+
+        page_size=P (a power of two >= 16; needs use_cache=True, fp32 storage): the KV cache is a
+        PagedKVCache whose pool holds the pages the batch can fill,
+        sum_b ceil(min(len_b + max_new_tokens, n_positions) / P), instead of B * n_positions rows.
+        Every row is reserved to that length before the first step, so the block table is fixed
+        while a graph is captured and replays (graph=True budgets at least 3 tokens per row, the
+        steps a capture runs). The ids are those of the contiguous cache."""
         prompts = [[int(t) for t in p] for p in prompts]
         if not prompts or any(len(p) == 0 for p in prompts):
             raise ValueError("generate needs at least one prompt and no empty prompt")
@@ -507,6 +555,15 @@ class DecoderLM(Module):
                 raise ValueError(f'kv_dtype must be None, "fp32", "bf16" or "fp8", got {kv_dtype!r}')
             if not use_cache:
                 raise ValueError("generate(kv_dtype=...) stores a quantised KV cache: it needs use_cache=True")
+        if page_size is not None:
+            if int(page_size) != page_size or page_size < 16 or page_size & (int(page_size) - 1):
+                raise ValueError(f"page_size must be a power of two >= 16, got {page_size}")
+            if not use_cache:
+                raise ValueError("generate(page_size=...) pages a KV cache: it needs use_cache=True")
+            if kv_dtype is not None:
+                raise ValueError("generate(page_size=...) stores fp32 pages: a quantised paged cache "
+                                 "(kv_dtype) is not supported")
+            page_size = int(page_size)
         if graph and not use_cache:
             raise ValueError("generate(graph=True) replays the cached decode step: it needs use_cache=True")
         if prefill_chunk is not None:
@@ -530,11 +587,12 @@ class DecoderLM(Module):
         try:
             if graph:
                 return self._generate_graph(prompts, max_new_tokens, eos_id, sampler, max(1, int(sync_every)),
-                                            prefill_chunk, kv_dtype)
+                                            prefill_chunk, kv_dtype, page_size)
             if temperature == 0.0:
                 sampler = None
             if use_cache:
-                return self._generate_cached(prompts, max_new_tokens, eos_id, sampler, prefill_chunk, kv_dtype)
+                return self._generate_cached(prompts, max_new_tokens, eos_id, sampler, prefill_chunk, kv_dtype,
+                                             page_size)
             return [self._generate_plain(p, max_new_tokens, eos_id, sampler) for p in prompts]
         finally:
             if was_training:
@@ -556,11 +614,31 @@ class DecoderLM(Module):
             new.append(nxt)
         return new
 
-    def _generate_cached(self, prompts, max_new_tokens, eos_id, sampler=None, prefill_chunk=None, kv_dtype=None):
+    # steps _generate_graph may run on a fresh cache beyond the prompt whatever max_new_tokens: the
+    # two warm-up steps of the capture and the captured step itself (their appends are undone by the
+    # restore, but each reserves its token's page first)
+    GRAPH_CAPTURE_STEPS = 3
+
+    def _paged_budget(self, lens, max_new_tokens, page_size, graph=False):
+        """(tokens per row, pages) a paged generate call can fill: row b holds at most
+        min(len_b + max_new_tokens, n_positions) tokens. graph=True: at least GRAPH_CAPTURE_STEPS
+        tokens past the prompt, so that capturing the step never needs a page the pool lacks (and
+        the table never changes inside a capture)."""
+        new = max(int(max_new_tokens), self.GRAPH_CAPTURE_STEPS if graph else 0)
+        final = np.minimum(lens + new, self.n_positions)
+        return final, int((-(-final // page_size)).sum())
+
+    def _generate_cached(self, prompts, max_new_tokens, eos_id, sampler=None, prefill_chunk=None, kv_dtype=None,
+                         page_size=None):
         B = len(prompts)
         lens = np.array([len(p) for p in prompts], dtype=np.int64)
         T = int(lens.max())
-        cache = self.new_cache(B, kv_dtype)
+        if page_size is None:
+            cache = self.new_cache(B, kv_dtype)
+        else:
+            final, n_pages = self._paged_budget(lens, max_new_tokens, page_size)
+            cache = self.new_cache(B, page_size=page_size, n_pages=n_pages)
+            cache.reserve(final)  # the table is final before the first step
         idx = np.zeros((B, T), dtype=datatype)
         for b, p in enumerate(prompts):
             idx[b, :len(p)] = p
@@ -631,7 +709,7 @@ class DecoderLM(Module):
         self.__dict__.pop("_decode_graphs", None)
 
     def _generate_graph(self, prompts, max_new_tokens, eos_id, sampler, sync_every, prefill_chunk=None,
-                        kv_dtype=None):
+                        kv_dtype=None, page_size=None):
         from .graphs import StepGraph
         if not self.use_flash_attention:
             raise ValueError("a KV cache needs use_flash_attention=True")
@@ -643,16 +721,23 @@ class DecoderLM(Module):
         temperature, top_k, seed = sampler
         graphs = self.__dict__.setdefault("_decode_graphs", {})
         slot = B if kv_dtype is None else (B, kv_dtype)  # a quantised cache has buffers and graphs of its own
+        if page_size is not None:
+            # a paged cache too, per page size and pool size (the captured launches hold the pools)
+            final, n_pages = self._paged_budget(lens, max_new_tokens, page_size, graph=True)
+            slot = (B, "paged", page_size, n_pages)
         entry = graphs.pop(slot, None)
         if entry is None:
             # per batch size: the buffers (one KVCache) and the graphs captured over them; the
             # last MAX_DECODE_BATCH_SIZES batch sizes are kept
             while len(graphs) >= self.MAX_DECODE_BATCH_SIZES:
                 graphs.pop(next(iter(graphs)))
-            entry = {"state": _DecodeState(self, B, kv_dtype), "graphs": {}}
+            entry = {"state": _DecodeState(self, B, kv_dtype, page_size, n_pages if page_size else None),
+                     "graphs": {}}
         graphs[slot] = entry  # most recently used last
         st = entry["state"]
         st.begin(temperature, top_k, eos_id, seed)
+        if page_size is not None:
+            st.cache.reserve(final)  # the table is final before the first step: nothing changes while a graph replays
         # eager: the prefill (the prompt length varies) and the first token
         T = int(lens.max())
         idx = np.zeros((B, T), dtype=datatype)
@@ -715,11 +800,11 @@ class _DecodeState:
     flags, the token history [B, n_positions] (no row returns more tokens than that), the step
     counter and the seed slot."""
 
-    def __init__(self, lm: DecoderLM, batch_size: int, kv_dtype=None):
+    def __init__(self, lm: DecoderLM, batch_size: int, kv_dtype=None, page_size=None, n_pages=None):
         import torch
         from .tensor import Tensor
         from .tensor_data import TensorData
-        self.cache = lm.new_cache(batch_size, kv_dtype)
+        self.cache = lm.new_cache(batch_size, kv_dtype, page_size, n_pages)
         self.ids_dev = torch.zeros(batch_size, dtype=torch.float32, device="cuda")
         self.ids = Tensor(TensorData(self.ids_dev, (batch_size, 1)), backend=lm.backend)
         self.ids_i32 = torch.zeros(batch_size, dtype=torch.int32, device="cuda")

@@ -60,6 +60,17 @@ and the append kernels alone for a 1-token step (mt_kv_cache_append fp32, mt_kv_
 Each leg rotates over enough cache copies of its own to exceed twice the Infinity Cache. The script
 exits non-zero unless, with Hkv = H, each quantised step is faster than the fp32 step of the same
 run by more than the 4 % box-to-box variation (t_quant * 1.04 < t_fp32).
+
+--paged-legs instead writes profiles/decode_paged_bench.json: per shape of KVQ_SHAPES, Hkv in {H, H/4}
+and dtype in {fp32, bf16}, Nq = 1, alternated in one process and swapping places each round:
+
+  contig    one mt_flash_attn_decode_gqa step on a contiguous cache: the yardstick of the same run
+  paged16   one mt_flash_attn_decode_paged step, P = 16, the pages of every row shuffled over the pool
+  paged128  the same with P = 128
+
+Each leg rotates over enough caches (pools) of its own to exceed twice the Infinity Cache. No gate: the
+ratios paged / contig are recorded. The memory side is recorded too: nbytes of a one-layer KVCache and of
+PagedKVCaches holding a ragged batch of one row of 4096 tokens and seven of 64.
 """
 import argparse
 import json
@@ -469,6 +480,106 @@ def kvq_legs(args, torch, _hip):
         raise SystemExit(f"a quantised-cache step is not faster than the fp32-cache step by more than 4 % at {slow}")
 
 
+PAGED_SIZES = (16, 128)
+
+
+def bench_paged(torch, _hip, B, H, L, d, name, rounds, warmup):
+    dt = torch.bfloat16 if name == "bf16" else torch.float32
+    es = 2 if name == "bf16" else 4
+    code = 1 if name == "bf16" else 0
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rnd = lambda *s: torch.randn(*s, generator=g, device="cuda", dtype=torch.float32).to(dt)  # noqa: E731
+    q = rnd(B, 1, H, d).permute(0, 2, 1, 3)
+    kvl = torch.full((B,), L, dtype=torch.int32, device="cuda")
+    o = torch.empty((B, 1, H, d), dtype=dt, device="cuda").permute(0, 2, 1, 3)
+    m, l = (torch.empty((B, H, 1), dtype=torch.float32, device="cuda") for _ in range(2))
+    rows = []
+    for Hkv in (H, H // 4):
+        kv_bytes = 2 * B * Hkv * L * d * es
+        nset = min(72, max(2, -(-2 * ICACHE // kv_bytes) + 1))
+        nsplit, span, tile = _hip.decode_splits(code, B, H, 1, L, d, Hkv=Hkv)
+        ws_bytes = _hip.decode_workspace_bytes(code, B, H, 1, L, d, Hkv=Hkv)
+        ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device="cuda")
+        legs = {}
+        sets = [(rnd(B, L, Hkv, d).permute(0, 2, 1, 3), rnd(B, L, Hkv, d).permute(0, 2, 1, 3)) for _ in range(nset)]
+
+        def contig(i, sets=sets):
+            kc, vc = sets[i % nset]
+            _hip.flash_decode(q, kc, vc, kv_len=kvl, causal=True, out=o, m=m, l=l, workspace=ws)
+        legs["contig"] = contig
+        for P in PAGED_SIZES:
+            W = L // P
+            assert W * P == L
+            assert _hip.decode_paged_splits(code, B, H, 1, W, P, d, Hkv=Hkv) == (nsplit, span, tile)
+            assert _hip.decode_paged_workspace_bytes(code, B, H, 1, W, P, d, Hkv=Hkv) == ws_bytes
+            # every page of the pool in use, handed out in a shuffled order
+            table = torch.randperm(B * W, generator=g, device="cuda").to(torch.int32).reshape(B, W).contiguous()
+            pools = [(rnd(B * W, P, Hkv, d).permute(0, 2, 1, 3), rnd(B * W, P, Hkv, d).permute(0, 2, 1, 3))
+                     for _ in range(nset)]
+
+            def paged(i, pools=pools, table=table):
+                kp, vp = pools[i % nset]
+                _hip.flash_decode_paged(q, kp, vp, table, kv_len=kvl, causal=True, out=o, m=m, l=l, workspace=ws)
+            legs[f"paged{P}"] = paged
+        inner = nset * -(-24 // nset)   # whole turns over the leg's cache sets
+        for fn in legs.values():
+            for _ in range(warmup):
+                _timed(torch, fn, inner)
+        times = {k: [] for k in legs}
+        names = list(legs)
+        for r in range(rounds):  # the legs alternate inside every round, swapping places
+            for k in names[r % len(names):] + names[:r % len(names)]:
+                times[k].append(_timed(torch, legs[k], inner))
+        med = {k: statistics.median(v) for k, v in times.items()}
+        alg = kv_bytes + 2 * B * H * d * es + 2 * ws_bytes
+        row = {"shape": [B, H, L, d], "dtype": name, "nq": 1, "kv_heads": Hkv, "group": H // Hkv, "rounds": rounds,
+               "kv_bytes": kv_bytes, "algorithmic_bytes": alg, "splits": nsplit, "span_keys": span, "tile_keys": tile,
+               "workspace_bytes": ws_bytes, "cache_sets_rotated": nset, "launches_per_timing": inner}
+        for k in names:
+            row.update({f"{k}_s_median": med[k], f"{k}_s_min": min(times[k]), f"{k}_s_max": max(times[k]),
+                        f"{k}_bytes_per_s": alg / med[k]})
+        for P in PAGED_SIZES:
+            row[f"paged{P}_over_contig_time"] = med[f"paged{P}"] / med["contig"]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del legs, sets, pools
+        torch.cuda.empty_cache()
+    return rows
+
+
+def paged_memory(minitorch, lengths=(4096,) + (64,) * 7, n_head=16, head_dim=64):
+    """nbytes of one-layer caches for a ragged batch: the contiguous KVCache pays B * n_positions rows,
+    a PagedKVCache the pages the rows fill."""
+    backend = minitorch.TensorBackend(minitorch.HipKernelOps)
+    B, npos = len(lengths), max(lengths)
+    plain = minitorch.KVCache(1, B, n_head, npos, head_dim, backend)
+    out = {"lengths": list(lengths), "n_layer": 1, "n_head": n_head, "head_dim": head_dim, "n_positions": npos,
+           "contiguous_nbytes": plain.nbytes}
+    del plain
+    for P in PAGED_SIZES:
+        pages = sum(-(-n // P) for n in lengths)
+        cache = minitorch.PagedKVCache(1, B, n_head, npos, head_dim, backend, page_size=P, n_pages=pages)
+        cache.reserve(lengths)
+        assert cache.pages_free == 0
+        out[f"paged{P}_pages"] = pages
+        out[f"paged{P}_nbytes"] = cache.nbytes
+        out[f"paged{P}_over_contiguous_bytes"] = cache.nbytes / out["contiguous_nbytes"]
+        del cache
+    return out
+
+
+def paged_legs(args, torch, minitorch, _hip):
+    res = {"device": torch.cuda.get_device_name(0), "kernels": [], "memory": paged_memory(minitorch)}
+    print(json.dumps(res["memory"]), flush=True)
+    torch.cuda.empty_cache()
+    for B, H, L, d in KVQ_SHAPES:
+        for name in ("f32", "bf16"):
+            res["kernels"] += bench_paged(torch, _hip, B, H, L, d, name, args.rounds, args.warmup)
+    os.makedirs(os.path.dirname(args.paged_out), exist_ok=True)
+    with open(args.paged_out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def bench_generate(minitorch, n_positions, prompt_len, new_tokens, batch, rounds):
     np.random.seed(0)
     backend = minitorch.TensorBackend(minitorch.HipKernelOps)
@@ -578,6 +689,9 @@ def main():
     ap.add_argument("--kvq-legs", action="store_true",
                     help="run the quantised-KV-cache decode legs instead, into --kvq-out")
     ap.add_argument("--kvq-out", default=os.path.join(ROOT, "profiles", "decode_kvq_bench.json"))
+    ap.add_argument("--paged-legs", action="store_true",
+                    help="run the paged-KV-cache decode legs instead, into --paged-out")
+    ap.add_argument("--paged-out", default=os.path.join(ROOT, "profiles", "decode_paged_bench.json"))
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--skip-generate", action="store_true")
@@ -595,6 +709,8 @@ def main():
         return extend_legs(args, torch, _hip)
     if args.kvq_legs:
         return kvq_legs(args, torch, _hip)
+    if args.paged_legs:
+        return paged_legs(args, torch, minitorch, _hip)
     res = {"device": torch.cuda.get_device_name(0), "kernels": [], "generate": []}
     for B, H, L, d, name in SHAPES:
         r = bench_shape(torch, _hip, B, H, L, d, name, args.rounds, args.warmup)
