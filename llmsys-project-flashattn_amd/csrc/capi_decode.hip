@@ -72,6 +72,23 @@ int aligned16(const char* what, const void* p, const int64_t s[3], int esize) {
 int64_t decode_ws_bytes(const DecodePlan& p, int64_t B, int64_t H, int64_t Nq, int64_t d) {
   return p.nsplit == 1 ? 0 : B * H * Nq * p.nsplit * (d + 2) * 4;
 }
+
+int decode_args(DecodeArgs& a, const DecodePlan& p, const char* ws_query, int causal, const void* q, const void* k,
+                const void* v, void* o, float* m, float* l, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk,
+                int64_t d, const int* kv_len, void* workspace, int64_t workspace_bytes) {
+  const int64_t need = decode_ws_bytes(p, B, H, Nq, d);
+  if (need > 0 && (!workspace || workspace_bytes < need))
+    return set_error("decode workspace too small: %lld bytes, %s gives %lld",
+                     (long long)(workspace ? workspace_bytes : 0), ws_query, (long long)need);
+  if (need > 0 && ((uintptr_t)workspace & 15)) return set_error("decode workspace is not 16-B aligned");
+  a.q = q; a.k = k; a.v = v; a.o = o; a.m = m; a.l = l;
+  a.ws = (float*)workspace; a.kv_len = kv_len;
+  a.H = (int)H; a.Nq = (int)Nq; a.Nk = (int)Nk; a.d = (int)d;
+  a.Hkv = (int)Hkv; a.gs = p.gs; a.slices = p.slices; a.rows = B * H * Nq;
+  a.nsplit = p.nsplit; a.span = p.span; a.causal = causal != 0;
+  a.scale_log2 = (float)(1.4426950408889634 / sqrt((double)d));
+  return 0;
+}
 }  // namespace mt
 
 using namespace mt;
@@ -101,14 +118,11 @@ int mt_flash_attn_decode_gqa(int dtype, int causal, const void* q, const void* k
   if (int rc = decode_sizes(dtype, B, H, Hkv, Nq, Nk, d)) return rc;
   const int esize = dtype == MT_F32 ? 4 : 2, osize = dtype == MT_BF16 ? 2 : 4;
   const DecodePlan p = decode_plan(esize, B, H, Hkv, Nq, Nk, d);
-  const int64_t need = decode_ws_bytes(p, B, H, Nq, d);
-  if (need > 0 && (!workspace || workspace_bytes < need))
-    return set_error("decode workspace too small: %lld bytes, mt_flash_attn_decode_workspace_bytes gives %lld",
-                     (long long)(workspace ? workspace_bytes : 0), (long long)need);
-  if (need > 0 && ((uintptr_t)workspace & 15)) return set_error("decode workspace is not 16-B aligned");
   DecodeArgs a;
-  a.q = q; a.k = k_cache; a.v = v_cache; a.o = o; a.m = m; a.l = l;
-  a.ws = (float*)workspace; a.kv_len = kv_len;
+  if (int rc = decode_args(a, p, "mt_flash_attn_decode_workspace_bytes", causal, q, k_cache, v_cache, o, m, l, B, H,
+                           Hkv, Nq, Nk, d, kv_len, workspace, workspace_bytes))
+    return rc;
+  a.o_f32 = osize == 4;
   strides_or_dense(a.qs, q_strides, H, Nq, d);
   strides_or_dense(a.ks, k_strides, Hkv, Nk, d);
   strides_or_dense(a.vs, v_strides, Hkv, Nk, d);
@@ -117,10 +131,6 @@ int mt_flash_attn_decode_gqa(int dtype, int causal, const void* q, const void* k
   if (int rc = aligned16("k_cache", k_cache, a.ks, esize)) return rc;
   if (int rc = aligned16("v_cache", v_cache, a.vs, esize)) return rc;
   if (int rc = aligned16("o", o, a.os, osize)) return rc;
-  a.H = (int)H; a.Nq = (int)Nq; a.Nk = (int)Nk; a.d = (int)d;
-  a.Hkv = (int)Hkv; a.gs = p.gs; a.slices = p.slices; a.rows = B * H * Nq;
-  a.nsplit = p.nsplit; a.span = p.span; a.causal = causal != 0; a.o_f32 = osize == 4;
-  a.scale_log2 = (float)(1.4426950408889634 / sqrt((double)d));
   return check_hip(launch_decode(a, esize == 2, B, (hipStream_t)stream), "mt_flash_attn_decode");
 }
 

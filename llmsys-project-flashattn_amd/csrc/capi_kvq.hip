@@ -37,14 +37,6 @@ static int kvq_decode_sizes(int kv_dtype, int64_t B, int64_t H, int64_t Hkv, int
   return kvq_sizes(kv_dtype, B, Hkv, Nk, d);
 }
 
-static void kvq_strides(int64_t dst[3], const int64_t* src, int64_t H, int64_t N, int64_t d) {
-  if (src) {
-    dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
-  } else {
-    dst[0] = H * N * d; dst[1] = N * d; dst[2] = d;
-  }
-}
-
 // base pointer and every stride a multiple of `bytes` (strides in elements of esize bytes)
 static int kvq_aligned(const char* what, const void* p, const int64_t s[3], int esize, int bytes) {
   if (!p) return set_error("%s is NULL", what);
@@ -67,9 +59,6 @@ static int kvq_scales(bool fp8, const void* k_scale, const void* v_scale) {
   return 0;
 }
 
-static int64_t kvq_ws_bytes(const DecodePlan& p, int64_t B, int64_t H, int64_t Nq, int64_t d) {
-  return p.nsplit == 1 ? 0 : B * H * Nq * p.nsplit * (d + 2) * 4;
-}
 }  // namespace mt
 
 using namespace mt;
@@ -88,7 +77,7 @@ int mt_flash_attn_decode_kvq_splits(int kv_dtype, int64_t B, int64_t H, int64_t 
 int64_t mt_flash_attn_decode_kvq_workspace_bytes(int kv_dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq,
                                                  int64_t Nk, int64_t d) {
   if (kvq_decode_sizes(kv_dtype, B, H, Hkv, Nq, Nk, d)) return -1;
-  return kvq_ws_bytes(decode_plan(2, B, H, Hkv, Nq, Nk, d), B, H, Nq, d);
+  return decode_ws_bytes(decode_plan(2, B, H, Hkv, Nq, Nk, d), B, H, Nq, d);
 }
 
 int mt_flash_attn_decode_kvq(int kv_dtype, int causal, const void* q, const void* k_cache, const void* v_cache,
@@ -101,28 +90,21 @@ int mt_flash_attn_decode_kvq(int kv_dtype, int causal, const void* q, const void
   const bool fp8 = kv_dtype == MT_KV_FP8;
   if (int rc = kvq_scales(fp8, k_scale, v_scale)) return rc;
   const DecodePlan p = decode_plan(2, B, H, Hkv, Nq, Nk, d);
-  const int64_t need = kvq_ws_bytes(p, B, H, Nq, d);
-  if (need > 0 && (!workspace || workspace_bytes < need))
-    return set_error("decode workspace too small: %lld bytes, mt_flash_attn_decode_kvq_workspace_bytes gives %lld",
-                     (long long)(workspace ? workspace_bytes : 0), (long long)need);
-  if (need > 0 && ((uintptr_t)workspace & 15)) return set_error("decode workspace is not 16-B aligned");
   KvqDecodeArgs ka;
   DecodeArgs& a = ka.d;
-  a.q = q; a.k = k_cache; a.v = v_cache; a.o = o; a.m = m; a.l = l;
-  a.ws = (float*)workspace; a.kv_len = kv_len;
+  if (int rc = decode_args(a, p, "mt_flash_attn_decode_kvq_workspace_bytes", causal, q, k_cache, v_cache, o, m, l, B,
+                           H, Hkv, Nq, Nk, d, kv_len, workspace, workspace_bytes))
+    return rc;
+  a.o_f32 = 1;
   ka.kscale = fp8 ? k_scale : nullptr; ka.vscale = fp8 ? v_scale : nullptr;
-  kvq_strides(a.qs, q_strides, H, Nq, d);
-  kvq_strides(a.ks, k_strides, Hkv, Nk, d);
-  kvq_strides(a.vs, v_strides, Hkv, Nk, d);
-  kvq_strides(a.os, o_strides, H, Nq, d);
+  strides_or_dense(a.qs, q_strides, H, Nq, d);
+  strides_or_dense(a.ks, k_strides, Hkv, Nk, d);
+  strides_or_dense(a.vs, v_strides, Hkv, Nk, d);
+  strides_or_dense(a.os, o_strides, H, Nq, d);
   if (int rc = kvq_aligned("q", q, a.qs, 4, 16)) return rc;
   if (int rc = kvq_cache_aligned("k_cache", k_cache, a.ks, fp8)) return rc;
   if (int rc = kvq_cache_aligned("v_cache", v_cache, a.vs, fp8)) return rc;
   if (int rc = kvq_aligned("o", o, a.os, 4, 16)) return rc;
-  a.H = (int)H; a.Nq = (int)Nq; a.Nk = (int)Nk; a.d = (int)d;
-  a.Hkv = (int)Hkv; a.gs = p.gs; a.slices = p.slices; a.rows = B * H * Nq;
-  a.nsplit = p.nsplit; a.span = p.span; a.causal = causal != 0; a.o_f32 = 1;
-  a.scale_log2 = (float)(1.4426950408889634 / sqrt((double)d));
   return check_hip(launch_decode_kvq(ka, fp8, B, (hipStream_t)stream), "mt_flash_attn_decode_kvq");
 }
 
@@ -141,10 +123,10 @@ int mt_kv_cache_append_quant(int kv_dtype, const float* k_new, const float* v_ne
   a.kn = k_new; a.vn = v_new; a.kc = (char*)k_cache; a.vc = (char*)v_cache;
   a.kscale = fp8 ? k_scale : nullptr; a.vscale = fp8 ? v_scale : nullptr;
   a.pos = pos;
-  kvq_strides(a.kns, knew_strides, Hkv, Nq, d);
-  kvq_strides(a.vns, vnew_strides, Hkv, Nq, d);
-  kvq_strides(a.kcs, kcache_strides, Hkv, Nmax, d);
-  kvq_strides(a.vcs, vcache_strides, Hkv, Nmax, d);
+  strides_or_dense(a.kns, knew_strides, Hkv, Nq, d);
+  strides_or_dense(a.vns, vnew_strides, Hkv, Nq, d);
+  strides_or_dense(a.kcs, kcache_strides, Hkv, Nmax, d);
+  strides_or_dense(a.vcs, vcache_strides, Hkv, Nmax, d);
   if (int rc = kvq_aligned("k_new", k_new, a.kns, 4, 4)) return rc;
   if (int rc = kvq_aligned("v_new", v_new, a.vns, 4, 4)) return rc;
   if (int rc = kvq_cache_aligned("k_cache", k_cache, a.kcs, fp8)) return rc;
@@ -174,10 +156,10 @@ int mt_kv_cache_dequant(int kv_dtype, const void* k_cache, const void* v_cache, 
   a.kc = (const char*)k_cache; a.vc = (const char*)v_cache;
   a.kscale = fp8 ? k_scale : nullptr; a.vscale = fp8 ? v_scale : nullptr;
   a.ko = k_out; a.vo = v_out; a.kv_len = kv_len;
-  kvq_strides(a.kcs, kcache_strides, Hkv, Nk, d);
-  kvq_strides(a.vcs, vcache_strides, Hkv, Nk, d);
-  kvq_strides(a.kos, kout_strides, Hkv, Nk, d);
-  kvq_strides(a.vos, vout_strides, Hkv, Nk, d);
+  strides_or_dense(a.kcs, kcache_strides, Hkv, Nk, d);
+  strides_or_dense(a.vcs, vcache_strides, Hkv, Nk, d);
+  strides_or_dense(a.kos, kout_strides, Hkv, Nk, d);
+  strides_or_dense(a.vos, vout_strides, Hkv, Nk, d);
   if (int rc = kvq_cache_aligned("k_cache", k_cache, a.kcs, fp8)) return rc;
   if (int rc = kvq_cache_aligned("v_cache", v_cache, a.vcs, fp8)) return rc;
   if (int rc = kvq_aligned("k_out", k_out, a.kos, 4, 16)) return rc;

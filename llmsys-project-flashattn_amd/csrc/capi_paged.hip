@@ -82,15 +82,12 @@ int mt_flash_attn_decode_paged(int dtype, int causal, const void* q, const void*
   if (int rc = paged_table(block_table)) return rc;
   const int esize = dtype == MT_F32 ? 4 : 2, osize = dtype == MT_BF16 ? 2 : 4;
   const DecodePlan p = decode_plan(esize, B, H, Hkv, Nq, Nk, d);
-  const int64_t need = decode_ws_bytes(p, B, H, Nq, d);
-  if (need > 0 && (!workspace || workspace_bytes < need))
-    return set_error("decode workspace too small: %lld bytes, mt_flash_attn_decode_paged_workspace_bytes gives %lld",
-                     (long long)(workspace ? workspace_bytes : 0), (long long)need);
-  if (need > 0 && ((uintptr_t)workspace & 15)) return set_error("decode workspace is not 16-B aligned");
   PagedDecodeArgs pa;
   DecodeArgs& a = pa.d;
-  a.q = q; a.k = k_pool; a.v = v_pool; a.o = o; a.m = m; a.l = l;
-  a.ws = (float*)workspace; a.kv_len = kv_len;
+  if (int rc = decode_args(a, p, "mt_flash_attn_decode_paged_workspace_bytes", causal, q, k_pool, v_pool, o, m, l, B,
+                           H, Hkv, Nq, Nk, d, kv_len, workspace, workspace_bytes))
+    return rc;
+  a.o_f32 = osize == 4;
   strides_or_dense(a.qs, q_strides, H, Nq, d);
   strides_or_dense(a.ks, k_strides, Hkv, P, d);
   strides_or_dense(a.vs, v_strides, Hkv, P, d);
@@ -99,10 +96,6 @@ int mt_flash_attn_decode_paged(int dtype, int causal, const void* q, const void*
   if (int rc = aligned16("k_pool", k_pool, a.ks, esize)) return rc;
   if (int rc = aligned16("v_pool", v_pool, a.vs, esize)) return rc;
   if (int rc = aligned16("o", o, a.os, osize)) return rc;
-  a.H = (int)H; a.Nq = (int)Nq; a.Nk = (int)Nk; a.d = (int)d;
-  a.Hkv = (int)Hkv; a.gs = p.gs; a.slices = p.slices; a.rows = B * H * Nq;
-  a.nsplit = p.nsplit; a.span = p.span; a.causal = causal != 0; a.o_f32 = osize == 4;
-  a.scale_log2 = (float)(1.4426950408889634 / sqrt((double)d));
   pa.table = block_table; pa.W = (int)W; pa.lgP = lgP; pa.n_pages = (int)n_pages;
   return check_hip(launch_decode_paged(pa, esize == 2, B, (hipStream_t)stream), "mt_flash_attn_decode_paged");
 }

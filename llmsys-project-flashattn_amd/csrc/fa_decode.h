@@ -1,6 +1,6 @@
-// Shared between fa_decode.hip (kernels, launchers), fa_kvq.hip and fa_paged.hip (the quantised-cache
-// and paged-cache kernels, which reuse the lane-group helpers and the combine pass) and capi_decode.hip
-// / capi_kvq.hip / capi_paged.hip (the C ABI).
+// Shared between fa_decode.hip, fa_kvq.hip and fa_paged.hip (the plain, quantised and paged caches:
+// each instantiates the one decode kernel of fa_decode_kernel.h on its source and owns its append
+// and copy kernels) and capi_decode.hip / capi_kvq.hip / capi_paged.hip (the C ABI).
 #pragma once
 #include "fa_common.h"
 
@@ -41,6 +41,12 @@ int decode_sizes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64
 void strides_or_dense(int64_t dst[3], const int64_t* src, int64_t H, int64_t N, int64_t d);
 int aligned16(const char* what, const void* p, const int64_t s[3], int esize);
 int64_t decode_ws_bytes(const DecodePlan& p, int64_t B, int64_t H, int64_t Nq, int64_t d);
+// what the three decode entry points do alike once the sizes are valid: the workspace check (ws_query
+// names the entry point's workspace query in the message) and the fields of `a` that are neither
+// strides nor o_f32; 0, or the error status with the message set
+int decode_args(DecodeArgs& a, const DecodePlan& p, const char* ws_query, int causal, const void* q, const void* k,
+                const void* v, void* o, float* m, float* l, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk,
+                int64_t d, const int* kv_len, void* workspace, int64_t workspace_bytes);
 
 constexpr int kDecWaves = 4;    // waves per workgroup
 constexpr int kDecUnroll = 4;   // key loads of K (and of V) in flight per wave and step
@@ -72,16 +78,20 @@ template <int LPK> __device__ __forceinline__ float group_sum(float v) {
 
 __device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
 
-// a 16-B chunk of a Q / K / V row widened to fp32 (fa_decode.hip, fa_paged.hip)
+// a 16-B chunk of a Q / K / V row, as loaded (Raw) and widened to fp32
+struct Chunk16 {
+  using Raw = uint4;
+  static __device__ __forceinline__ Raw zero() { return make_uint4(0u, 0u, 0u, 0u); }
+};
 template <typename T> struct Chunk;
-template <> struct Chunk<float> {
+template <> struct Chunk<float> : Chunk16 {
   static constexpr int N = 4;
   static __device__ __forceinline__ void unpack(const uint4& u, float* f) {
     f[0] = __builtin_bit_cast(float, u.x); f[1] = __builtin_bit_cast(float, u.y);
     f[2] = __builtin_bit_cast(float, u.z); f[3] = __builtin_bit_cast(float, u.w);
   }
 };
-template <> struct Chunk<bf16> {
+template <> struct Chunk<bf16> : Chunk16 {
   static constexpr int N = 8;
   static __device__ __forceinline__ void unpack(const uint4& u, float* f) {
     const unsigned w[4] = {u.x, u.y, u.z, u.w};

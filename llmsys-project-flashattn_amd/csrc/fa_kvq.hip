@@ -6,33 +6,26 @@
 // 0x7F / 0xFF, what v_cvt_pk_f32_fp8 reads on gfx950). An fp8 row has one fp32 scale s (dense
 // [B, Hkv, Nmax] arrays): the row's values are s * e4m3(code). bf16 rows have no scale.
 //
-// fa_decode_partial_kvq is fa_decode_partial (fa_decode.hip) with a cache element type of its own:
-// the same grid, spans, row packing, masking by selects, online softmax, DPP group sums, wave and
-// LDS merges, workspace layout and combine pass (fa_decode_combine, reused as it is). A key row is
-// C = d / 8 chunks of 8 elements for both formats (a 16-B load of bf16, an 8-B load of fp8; a
-// 16-B fp8 chunk would put 16 fp32 Q and accumulator elements per query row in every lane, 256
-// VGPRs at NQ = 8), so LPK and the plan are those of a bf16 cache. A lane's chunk is dequantised
-// to fp32 in registers. The fp8 scale of key j multiplies the logit after the group sum
-// (dot * k_scale[j] * scale_log2) and p before the PV fma; a key at or past the span's end re-reads
-// the scale of the last visible row, as it does the row, and both are replaced by selects.
+// Decode is the shared kernel (fa_decode_kernel.h) on KvqSrc below: the plan, arithmetic and combine
+// pass of a plain cache. A key row is C = d / 8 chunks of 8 elements for both formats (a 16-B load
+// of bf16, an 8-B load of fp8; a 16-B fp8 chunk would put 16 fp32 Q and accumulator elements per
+// query row in every lane, 256 VGPRs at NQ = 8), so LPK and the plan are those of a bf16 cache. A
+// lane's chunk is dequantised to fp32 in registers. The fp8 scale of key j multiplies the logit after
+// the group sum (dot * k_scale[j] * scale_log2) and p before the PV fma; a key at or past the span's
+// end re-reads the scale of the last visible row, as it does the row, and both are replaced by selects.
 #include "fa_kvq.h"
+#include "fa_decode_kernel.h"
 #include <algorithm>
 
 namespace mt {
 
-struct KvBf16 {
-  using Raw = uint4;
+struct KvBf16 : Chunk<bf16> {
   static constexpr int kBytes = 2;
   static constexpr bool kScaled = false;
-  static __device__ __forceinline__ Raw zero() { return make_uint4(0u, 0u, 0u, 0u); }
-  static __device__ __forceinline__ void unpack(const Raw& u, float* f) {
-    const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f[2 * i] = __builtin_bit_cast(float, w[i] << 16);
-      f[2 * i + 1] = __builtin_bit_cast(float, w[i] & 0xffff0000u);
-    }
-  }
+  // the zero of a masked key's select (fa_decode_kernel.h, "masked"): a fresh value here, the named
+  // one for fp8 -- per format, the spelling under which every instantiation keeps the registers,
+  // AGPRs and waves per SIMD recorded in profiles/decode_kernels_resources.txt
+  static __device__ __forceinline__ Raw masked(const Raw&) { return zero(); }
 };
 
 struct KvFp8 {
@@ -40,6 +33,7 @@ struct KvFp8 {
   static constexpr int kBytes = 1;
   static constexpr bool kScaled = true;
   static __device__ __forceinline__ Raw zero() { return make_uint2(0u, 0u); }
+  static __device__ __forceinline__ const Raw& masked(const Raw& z) { return z; }
   static __device__ __forceinline__ void unpack(const Raw& u, float* f) {
     typedef __attribute__((ext_vector_type(2))) float f32x2;
     const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)u.x, false);
@@ -53,266 +47,61 @@ struct KvFp8 {
 
 constexpr int kKvqEpc = 8;  // elements per chunk, both formats
 
-template <typename KV, int LPK, int NQ>
-__global__ __launch_bounds__(kDecWaves * 64) void fa_decode_partial_kvq(const KvqDecodeArgs ka_) {
+// A contiguous cache of bf16 or fp8 rows (strides in storage elements) under fp32 Q and O
+template <typename KV> struct KvqSrc : KV {
+  using Args = KvqDecodeArgs;
   using Raw = typename KV::Raw;
-  constexpr int EPC = kKvqEpc;
-  constexpr int GROUPS = 64 / LPK;       // keys per wave-wide load
-  constexpr int TILE = kDecUnroll * GROUPS;
-  constexpr int DP = LPK * EPC;          // padded head dim of the LDS image
-  __shared__ float s_o[kDecWaves][NQ][DP];
-  __shared__ float s_ml[kDecWaves][NQ][2];
-  const DecodeArgs& a = ka_.d;
-
-  const int split = blockIdx.y;
-  const int bk = blockIdx.x / a.slices, slice = blockIdx.x - bk * a.slices;
-  const int b = bk / a.Hkv, hkv = bk - b * a.Hkv;
-  const int G = a.H / a.Hkv;
-  const int h0 = hkv * G + slice * a.gs;     // first query head of this workgroup
-  const int nh = min(a.gs, G - slice * a.gs);  // its heads (fewer in a ragged last slice)
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int c = lane % LPK, g = lane / LPK;
-  const int C = a.d / EPC;               // real chunks per row (<= LPK)
-  const int d4 = a.d / 4;
-
-  int n = a.Nk;
-  if (a.kv_len) n = min(max(a.kv_len[b], 0), a.Nk);
-  const int k0 = split * a.span;
-  const int kend = min(k0 + a.span, n);
-  const bool final_out = a.nsplit == 1;
-  const int64_t row0 = ((int64_t)b * a.H + h0) * a.Nq;  // first (b, h, query) row
-
-  if (k0 < kend) {  // workgroup-uniform
-    int lim[NQ];
-    float qf[NQ][EPC];
-    int hh = 0, qi = 0;  // register row i is head h0 + hh, query qi
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      const bool row = NQ == 1 || hh < nh;  // nh >= 1
-      lim[i] = row ? min(a.causal ? n - a.Nq + 1 + qi : n, kend) : 0;
-      float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
-      if (row && c < C) {
-        const float* qp = (const float*)a.q + (int64_t)b * a.qs[0] + (int64_t)(h0 + hh) * a.qs[1] +
-                          (int64_t)qi * a.qs[2] + c * EPC;
-        x = *(const float4*)qp;
-        y = *(const float4*)(qp + 4);
-      }
-      qf[i][0] = x.x; qf[i][1] = x.y; qf[i][2] = x.z; qf[i][3] = x.w;
-      qf[i][4] = y.x; qf[i][5] = y.y; qf[i][6] = y.z; qf[i][7] = y.w;
-      if (++qi == a.Nq) { qi = 0; ++hh; }
+  using Q = float;
+  static constexpr int EPC = kKvqEpc;
+  static constexpr int kMaxLpk = 32;  // d <= 256: at most 32 chunks of 8
+  static constexpr int waves_per_eu(int, int) { return 1; }
+  static __host__ __device__ __forceinline__ const DecodeArgs& base(const Args& sa) { return sa.d; }
+  struct QChunk {  // 8 fp32 elements
+    float4 x, y;
+    __device__ __forceinline__ QChunk() : x(make_float4(0.f, 0.f, 0.f, 0.f)), y(x) {}
+    explicit __device__ __forceinline__ QChunk(const float* p) : x(*(const float4*)p), y(*(const float4*)(p + 4)) {}
+    __device__ __forceinline__ void unpack(float* f) const {
+      f[0] = x.x; f[1] = x.y; f[2] = x.z; f[3] = x.w;
+      f[4] = y.x; f[5] = y.y; f[6] = y.z; f[7] = y.w;
     }
-    float m[NQ], l[NQ], acc[NQ][EPC];
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      m[i] = -INFINITY;
-      l[i] = 0.f;
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) acc[i][e] = 0.f;
-    }
-    // byte addresses: the strides are in storage elements
-    const char* kb = (const char*)a.k + ((int64_t)b * a.ks[0] + (int64_t)hkv * a.ks[1]) * KV::kBytes;
-    const char* vb = (const char*)a.v + ((int64_t)b * a.vs[0] + (int64_t)hkv * a.vs[1]) * KV::kBytes;
-    const int64_t srow = ((int64_t)b * a.Hkv + hkv) * a.Nk;  // this head's row scales
-    const int cc = c < C ? c : 0;  // a lane past the row's chunks re-reads chunk 0 (values dropped)
-
-    // the loads of one tile: K then V chunks of kDecUnroll x GROUPS keys and (fp8) their row scales.
-    // Keys at or past kend re-read row kend - 1 (in [k0, n): a visible, initialised row) and its
-    // scales; their values are dropped below
-    auto issue = [&](int t0, Raw* ku, Raw* vu, float* ks, float* vs) {
-#pragma unroll
-      for (int u = 0; u < kDecUnroll; ++u) {
-        const int kk = min(t0 + u * GROUPS + g, kend - 1);
-        ku[u] = *(const Raw*)(kb + ((int64_t)kk * a.ks[2] + cc * EPC) * KV::kBytes);
-        if constexpr (KV::kScaled) ks[u] = ka_.kscale[srow + kk];
-      }
-#pragma unroll
-      for (int u = 0; u < kDecUnroll; ++u) {
-        const int kk = min(t0 + u * GROUPS + g, kend - 1);
-        vu[u] = *(const Raw*)(vb + ((int64_t)kk * a.vs[2] + cc * EPC) * KV::kBytes);
-        if constexpr (KV::kScaled) vs[u] = ka_.vscale[srow + kk];
-      }
-    };
-    constexpr bool kAhead = NQ <= 4;
-    auto consume = [&](int t0, const Raw* ku, const Raw* vu, const float* ks, const float* vs) {
-      int key[kDecUnroll];
-#pragma unroll
-      for (int u = 0; u < kDecUnroll; ++u) key[u] = t0 + u * GROUPS + g;
-      float s[NQ][kDecUnroll];
-#pragma unroll
-      for (int u = 0; u < kDecUnroll; ++u) {
-        const bool live = key[u] < kend && c < C;
-        const Raw kx = live ? ku[u] : KV::zero();
-        float kf[EPC];
-        KV::unpack(kx, kf);
-        float sc = a.scale_log2;
-        if constexpr (KV::kScaled) sc = (key[u] < kend ? ks[u] : 0.f) * a.scale_log2;
-#pragma unroll
-        for (int i = 0; i < NQ; ++i) {
-          float dot = 0.f;
-#pragma unroll
-          for (int e = 0; e < EPC; ++e) dot = fmaf(qf[i][e], kf[e], dot);
-          dot = group_sum<LPK>(dot) * sc;
-          s[i][u] = key[u] < lim[i] ? dot : -INFINITY;  // select: a masked key's data decides nothing
-        }
-      }
-      float p[NQ][kDecUnroll];
-#pragma unroll
-      for (int i = 0; i < NQ; ++i) {
-        float mx = m[i];
-#pragma unroll
-        for (int u = 0; u < kDecUnroll; ++u) mx = fmaxf(mx, s[i][u]);
-        const float ms = mx == -INFINITY ? 0.f : mx;  // no visible key yet: exp2(-inf - 0) = 0
-        const float alpha = exp2_fast(m[i] - ms);
-        m[i] = mx;
-        float sum = 0.f;
-#pragma unroll
-        for (int u = 0; u < kDecUnroll; ++u) {
-          p[i][u] = exp2_fast(s[i][u] - ms);
-          sum += p[i][u];
-        }
-        l[i] = l[i] * alpha + sum;
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) acc[i][e] *= alpha;
-      }
-#pragma unroll
-      for (int u = 0; u < kDecUnroll; ++u) {
-        const bool live = key[u] < kend && c < C;
-        const Raw vx = live ? vu[u] : KV::zero();
-        float vf[EPC];
-        KV::unpack(vx, vf);
-        float vsc = 1.f;
-        if constexpr (KV::kScaled) vsc = key[u] < kend ? vs[u] : 0.f;
-#pragma unroll
-        for (int i = 0; i < NQ; ++i) {
-          const float pv = KV::kScaled ? p[i][u] * vsc : p[i][u];
-#pragma unroll
-          for (int e = 0; e < EPC; ++e) acc[i][e] = fmaf(pv, vf[e], acc[i][e]);
-        }
-      }
-    };
-    constexpr int STEP = kDecWaves * TILE;
-    Raw ka[kDecUnroll], va[kDecUnroll];
-    float ksa[kDecUnroll], vsa[kDecUnroll];
-    if constexpr (kAhead) {
-      // two register sets used in turn (no copies: a copy would wait for the tile just issued)
-      Raw kb2[kDecUnroll], vb2[kDecUnroll];
-      float ksb[kDecUnroll], vsb[kDecUnroll];
-      int t0 = k0 + wave * TILE;
-      if (t0 < kend) issue(t0, ka, va, ksa, vsa);
-      while (t0 < kend) {
-        issue(t0 + STEP, kb2, vb2, ksb, vsb);
-        __builtin_amdgcn_sched_barrier(0);  // keep the loads ahead of the arithmetic
-        consume(t0, ka, va, ksa, vsa);
-        t0 += STEP;
-        if (t0 >= kend) break;
-        issue(t0 + STEP, ka, va, ksa, vsa);
-        __builtin_amdgcn_sched_barrier(0);
-        consume(t0, kb2, vb2, ksb, vsb);
-        t0 += STEP;
-      }
-    } else {
-      for (int t0 = k0 + wave * TILE; t0 < kend; t0 += STEP) {
-        issue(t0, ka, va, ksa, vsa);
-        consume(t0, ka, va, ksa, vsa);
-      }
-    }
-
-    // merge the key groups of the wave (lane offsets LPK, 2 LPK, ...: the same chunk of other keys)
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      float mx = m[i];
-#pragma unroll
-      for (int off = LPK; off < 64; off *= 2) mx = fmaxf(mx, __shfl_xor(mx, off));
-      const float ms = mx == -INFINITY ? 0.f : mx;
-      const float w = exp2_fast(m[i] - ms);
-      float ls = l[i] * w;
-#pragma unroll
-      for (int off = LPK; off < 64; off *= 2) ls += __shfl_xor(ls, off);
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) {
-        float x = acc[i][e] * w;
-#pragma unroll
-        for (int off = LPK; off < 64; off *= 2) x += __shfl_xor(x, off);
-        acc[i][e] = x;
-      }
-      if (g == 0) {
-#pragma unroll
-        for (int e = 0; e < EPC; e += 4)
-          *(float4*)&s_o[wave][i][c * EPC + e] = make_float4(acc[i][e], acc[i][e + 1], acc[i][e + 2], acc[i][e + 3]);
-        if (c == 0) {
-          s_ml[wave][i][0] = mx;
-          s_ml[wave][i][1] = ls;
-        }
-      }
-    }
-    __syncthreads();
+  };
+  static __device__ __forceinline__ void store_o(const DecodeArgs& a, int64_t e, const float4& x) {
+    *(float4*)((float*)a.o + e) = x;
   }
 
-  // merge the waves (fixed order) and write this split's result, 4 O elements per thread
-  const bool empty = !(k0 < kend);
-  for (int idx = tid; idx < nh * a.Nq * d4; idx += kDecWaves * 64) {
-    const int i = idx / d4, e4 = idx - i * d4;  // register row i: head h0 + i / Nq, query i % Nq
-    const int hh = NQ == 1 ? 0 : i / a.Nq, qi = i - hh * a.Nq;
-    float mx = -INFINITY, ls = 0.f;
-    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!empty) {
+  const Args& sa;
+  const char* kb; const char* vb;  // this (b, hkv)'s rows, byte addresses
+  int64_t srow;                    // and row scales
+  int cc;                          // a lane past the row's chunks re-reads chunk 0 (values dropped)
+  __device__ __forceinline__ KvqSrc(const Args& sa_, int b, int hkv, int c, int C)
+      : sa(sa_),
+        kb((const char*)sa_.d.k + ((int64_t)b * sa_.d.ks[0] + (int64_t)hkv * sa_.d.ks[1]) * KV::kBytes),
+        vb((const char*)sa_.d.v + ((int64_t)b * sa_.d.vs[0] + (int64_t)hkv * sa_.d.vs[1]) * KV::kBytes),
+        srow(((int64_t)b * sa_.d.Hkv + hkv) * sa_.d.Nk),
+        cc(c < C ? c : 0) {}
+  template <int GROUPS>
+  __device__ __forceinline__ void issue(int t0, int g, int kend, Raw* ku, Raw* vu, float* ks, float* vs) const {
+    const DecodeArgs& a = sa.d;
 #pragma unroll
-      for (int w = 0; w < kDecWaves; ++w) mx = fmaxf(mx, s_ml[w][i][0]);
-      const float ms = mx == -INFINITY ? 0.f : mx;
-#pragma unroll
-      for (int w = 0; w < kDecWaves; ++w) {
-        const float f = exp2_fast(s_ml[w][i][0] - ms);
-        const float4 x = *(const float4*)&s_o[w][i][4 * e4];
-        ls += s_ml[w][i][1] * f;
-        o.x += x.x * f; o.y += x.y * f; o.z += x.z * f; o.w += x.w * f;
-      }
+    for (int u = 0; u < kDecUnroll; ++u) {
+      const int kk = min(t0 + u * GROUPS + g, kend - 1);
+      ku[u] = *(const Raw*)(kb + ((int64_t)kk * a.ks[2] + cc * EPC) * KV::kBytes);
+      if constexpr (KV::kScaled) ks[u] = sa.kscale[srow + kk];
     }
-    if (final_out) {
-      const float inv = ls > 0.f ? 1.f / ls : 0.f;
-      o.x *= inv; o.y *= inv; o.z *= inv; o.w *= inv;
-      *(float4*)((float*)a.o + (int64_t)b * a.os[0] + (int64_t)(h0 + hh) * a.os[1] + (int64_t)qi * a.os[2] + 4 * e4) = o;
-      if (e4 == 0) {
-        if (a.m) a.m[row0 + i] = mx * kLn2;
-        if (a.l) a.l[row0 + i] = ls;
-      }
-    } else {
-      const int64_t r = (row0 + i) * a.nsplit + split;
-      *(float4*)(a.ws + r * a.d + 4 * e4) = o;
-      if (e4 == 0) {
-        float* ml = a.ws + a.rows * a.nsplit * a.d + 2 * r;
-        ml[0] = mx;
-        ml[1] = ls;
-      }
+#pragma unroll
+    for (int u = 0; u < kDecUnroll; ++u) {
+      const int kk = min(t0 + u * GROUPS + g, kend - 1);
+      vu[u] = *(const Raw*)(vb + ((int64_t)kk * a.vs[2] + cc * EPC) * KV::kBytes);
+      if constexpr (KV::kScaled) vs[u] = sa.vscale[srow + kk];
     }
   }
-}
-
-template <typename KV, int LPK> static hipError_t launch_kvq_nq(const KvqDecodeArgs& a, dim3 grid, hipStream_t st) {
-  const int rows = a.d.gs * a.d.Nq;  // register rows of a workgroup
-  if (rows == 1) fa_decode_partial_kvq<KV, LPK, 1><<<grid, kDecWaves * 64, 0, st>>>(a);
-  else if (rows <= 4) fa_decode_partial_kvq<KV, LPK, 4><<<grid, kDecWaves * 64, 0, st>>>(a);
-  else fa_decode_partial_kvq<KV, LPK, 8><<<grid, kDecWaves * 64, 0, st>>>(a);
-  return hipGetLastError();
-}
-
-template <typename KV> static hipError_t launch_kvq_partial(const KvqDecodeArgs& a, int lpk, dim3 grid, hipStream_t st) {
-  switch (lpk) {
-    case 4: return launch_kvq_nq<KV, 4>(a, grid, st);
-    case 8: return launch_kvq_nq<KV, 8>(a, grid, st);
-    case 16: return launch_kvq_nq<KV, 16>(a, grid, st);
-    case 32: return launch_kvq_nq<KV, 32>(a, grid, st);  // d <= 256: at most 32 chunks of 8
-  }
-  return hipErrorInvalidValue;
-}
+};
 
 // Sizes are validated by the caller (capi_kvq.hip); the plan is decode_plan's for 2-byte elements
 // (8-element chunks) whatever the format.
 hipError_t launch_decode_kvq(const KvqDecodeArgs& a, bool fp8, int64_t B, hipStream_t st) {
   const int lpk = decode_lpk(a.d.d, 2);
-  const dim3 grid((unsigned)(B * a.d.Hkv * a.d.slices), (unsigned)a.d.nsplit);
-  hipError_t e = fp8 ? launch_kvq_partial<KvFp8>(a, lpk, grid, st) : launch_kvq_partial<KvBf16>(a, lpk, grid, st);
-  if (e != hipSuccess || a.d.nsplit == 1) return e;
-  return launch_decode_combine(a.d, B, st);
+  return fp8 ? launch_decode_src<KvqSrc<KvFp8>>(a, lpk, B, st) : launch_decode_src<KvqSrc<KvBf16>>(a, lpk, B, st);
 }
 
 // ---- quantising append ----------------------------------------------------------------------
