@@ -238,7 +238,17 @@ int mt_kv_cache_append(int dtype, const void* k_new, const void* v_new, void* k_
  *
  * mt_kv_cache_dequant: writes the fp32 rows j < clamp(kv_len[b], 0, Nk) (kv_len NULL: Nk) of
  * k_out / v_out ([B, Hkv, Nk, d] through strides in elements, 16-B rows): bf16 widened, fp8
- * e4m3(code) * scale (one fp32 product). Rows at or past that count are neither read nor written. */
+ * e4m3(code) * scale (one fp32 product). Rows at or past that count are neither read nor written.
+ *
+ * mt_flash_attn_extend_kvq: mt_flash_attn_extend's contract (any 1 <= Nq <= Nk, q_len, bottom-right
+ * causal alignment, (0, -inf, 0) for a query >= t or one with no visible key, one plain launch, no
+ * workspace, a launch that is a function of the sizes alone) with fp32 q / o / m / l and quantised
+ * caches read in place: rows are loaded in chunks of 8 elements and widened in registers with
+ * mt_kv_cache_dequant's formulas, so O, m and l have the bits of mt_flash_attn_extend(MT_F32) on
+ * the fp32 cache that mt_kv_cache_dequant writes from the same rows. Rows j >= n are never loaded
+ * and their scales neither. mt_flash_attn_extend_kvq_plan answers as mt_flash_attn_extend_plan does
+ * for MT_F32 at the same sizes. Refused: whatever mt_flash_attn_extend refuses for MT_F32 (Nq > Nk
+ * included) and the cache arguments this block's first paragraph lists. */
 enum { MT_KV_BF16 = 1, MT_KV_FP8 = 2 };
 int mt_flash_attn_decode_kvq_splits(int kv_dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk,
                                     int64_t d, int64_t* span_keys, int64_t* tile_keys);
@@ -250,6 +260,13 @@ int mt_flash_attn_decode_kvq(int kv_dtype, int causal, const void* q, const void
                              const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
                              const int64_t* o_strides, const int* kv_len,
                              void* workspace, int64_t workspace_bytes, void* stream);
+int mt_flash_attn_extend_kvq_plan(int kv_dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk,
+                                  int64_t d, int64_t* block_queries, int64_t* tile_keys);
+int mt_flash_attn_extend_kvq(int kv_dtype, int causal, const void* q, const void* k_cache, const void* v_cache,
+                             const float* k_scale, const float* v_scale, void* o, float* m, float* l,
+                             int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d,
+                             const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                             const int64_t* o_strides, const int* kv_len, const int* q_len, void* stream);
 int mt_kv_cache_append_quant(int kv_dtype, const float* k_new, const float* v_new, void* k_cache, void* v_cache,
                              float* k_scale, float* v_scale, int64_t B, int64_t Hkv, int64_t Nq, int64_t Nmax,
                              int64_t d, const int64_t* knew_strides, const int64_t* vnew_strides,
@@ -297,7 +314,20 @@ int mt_kv_cache_dequant(int kv_dtype, const void* k_cache, const void* v_cache, 
  * mt_kv_cache_gather_paged: writes the rows j < clamp(kv_len[b], 0, W * P) (kv_len NULL: W * P) of
  * the contiguous k_out / v_out ([B, Hkv, W * P, d] through strides in elements, 16-B rows) from
  * the pools. Rows at or past that count are neither read nor written (and no table entry at
- * index >= ceil(n / P) is read). */
+ * index >= ceil(n / P) is read).
+ *
+ * mt_flash_attn_extend_paged: mt_flash_attn_extend's contract (dtypes, any 1 <= Nq <= Nk = W * P,
+ * q_len, bottom-right causal alignment, (0, -inf, 0) for a query >= t or one with no visible key,
+ * one plain launch, no workspace) on a paged cache read in place, the page resolved per loaded
+ * row, so P may be smaller or larger than a key tile. The launch is a function of the sizes alone,
+ * never of kv_len, q_len or the table's contents; mt_flash_attn_extend_paged_plan answers as
+ * mt_flash_attn_extend_plan does at Nk = W * P. The arithmetic and its order are the plain kernel's:
+ * O, m and l have the bits mt_flash_attn_extend gives on a contiguous cache that holds the same
+ * rows. No table entry at index >= ceil(n / P) is read and no pool row of a key >= n. As in decode,
+ * an entry outside [0, n_pages), a negative one included, is NOT detected but clamped into the
+ * range (a negative one reads the last page): a silently wrong result, never an address outside
+ * the pool. Refused: whatever mt_flash_attn_extend refuses at Nk = W * P and the geometry and
+ * table arguments listed above. */
 int mt_flash_attn_decode_paged_splits(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t W,
                                       int64_t P, int64_t d, int64_t* span_keys, int64_t* tile_keys);
 int64_t mt_flash_attn_decode_paged_workspace_bytes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq,
@@ -308,6 +338,13 @@ int mt_flash_attn_decode_paged(int dtype, int causal, const void* q, const void*
                                const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides,
                                const int* block_table, const int* kv_len,
                                void* workspace, int64_t workspace_bytes, void* stream);
+int mt_flash_attn_extend_paged_plan(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t W,
+                                    int64_t P, int64_t d, int64_t* block_queries, int64_t* tile_keys);
+int mt_flash_attn_extend_paged(int dtype, int causal, const void* q, const void* k_pool, const void* v_pool,
+                               void* o, float* m, float* l, int64_t B, int64_t H, int64_t Hkv, int64_t Nq,
+                               int64_t W, int64_t P, int64_t n_pages, int64_t d, const int64_t* q_strides,
+                               const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides,
+                               const int* block_table, const int* kv_len, const int* q_len, void* stream);
 int mt_kv_cache_append_paged(int dtype, const void* k_new, const void* v_new, void* k_pool, void* v_pool,
                              int64_t B, int64_t Hkv, int64_t Nq, int64_t W, int64_t P, int64_t n_pages, int64_t d,
                              const int64_t* knew_strides, const int64_t* vnew_strides,

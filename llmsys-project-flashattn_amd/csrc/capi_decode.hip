@@ -30,7 +30,7 @@ int decode_sizes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64
 }
 
 // the extend step's sizes: decode's rules with 1 <= Nq <= Nk in place of Nq <= 8
-static int extend_sizes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d) {
+int extend_sizes(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d) {
   if (dtype != MT_F32 && dtype != MT_BF16 && dtype != MT_BF16_F32OUT)
     return set_error("unsupported dtype %d", dtype);
   if (B <= 0 || H <= 0 || Nk <= 0 || d <= 0)
@@ -67,6 +67,15 @@ int aligned16(const char* what, const void* p, const int64_t s[3], int esize) {
   for (int i = 0; i < 3; ++i)
     if (s[i] % epc) return set_error("%s stride %d (%lld elements) is not a multiple of 16 B", what, i, (long long)s[i]);
   return 0;
+}
+
+void extend_args(ExtendArgs& a, int esize, int causal, float* m, float* l, int64_t H, int64_t Hkv, int64_t Nq,
+                 int64_t Nk, int64_t d, const int* kv_len, const int* q_len) {
+  a.m = m; a.l = l; a.kv_len = kv_len; a.q_len = q_len;
+  a.H = (int)H; a.Hkv = (int)Hkv; a.Nq = (int)Nq; a.Nk = (int)Nk; a.d = (int)d;
+  a.nqb = (int)((Nq + extend_plan(esize, d).bq - 1) / extend_plan(esize, d).bq);
+  a.causal = causal != 0;
+  a.scale_log2 = (float)(1.4426950408889634 / sqrt((double)d));
 }
 
 int64_t decode_ws_bytes(const DecodePlan& p, int64_t B, int64_t H, int64_t Nq, int64_t d) {
@@ -168,8 +177,7 @@ int mt_flash_attn_extend(int dtype, int causal, const void* q, const void* k_cac
   if (int rc = extend_sizes(dtype, B, H, Hkv, Nq, Nk, d)) return rc;
   const int esize = dtype == MT_F32 ? 4 : 2, osize = dtype == MT_BF16 ? 2 : 4;
   ExtendArgs a;
-  a.q = q; a.k = k_cache; a.v = v_cache; a.o = o; a.m = m; a.l = l;
-  a.kv_len = kv_len; a.q_len = q_len;
+  a.q = q; a.k = k_cache; a.v = v_cache; a.o = o;
   strides_or_dense(a.qs, q_strides, H, Nq, d);
   strides_or_dense(a.ks, k_strides, Hkv, Nk, d);
   strides_or_dense(a.vs, v_strides, Hkv, Nk, d);
@@ -178,10 +186,8 @@ int mt_flash_attn_extend(int dtype, int causal, const void* q, const void* k_cac
   if (int rc = aligned16("k_cache", k_cache, a.ks, esize)) return rc;
   if (int rc = aligned16("v_cache", v_cache, a.vs, esize)) return rc;
   if (int rc = aligned16("o", o, a.os, osize)) return rc;
-  a.H = (int)H; a.Hkv = (int)Hkv; a.Nq = (int)Nq; a.Nk = (int)Nk; a.d = (int)d;
-  a.nqb = (int)((Nq + extend_plan(esize, d).bq - 1) / extend_plan(esize, d).bq);
-  a.causal = causal != 0; a.o_f32 = osize == 4;
-  a.scale_log2 = (float)(1.4426950408889634 / sqrt((double)d));
+  extend_args(a, esize, causal, m, l, H, Hkv, Nq, Nk, d, kv_len, q_len);
+  a.o_f32 = osize == 4;
   return check_hip(launch_extend(a, esize == 2, B, (hipStream_t)stream), "mt_flash_attn_extend");
 }
 

@@ -1,8 +1,10 @@
 // C ABI of the quantised KV cache (include/minitorch_hip.h): mt_flash_attn_decode_kvq with its
-// split / workspace queries, mt_kv_cache_append_quant and mt_kv_cache_dequant. Kernels: fa_kvq.hip.
+// split / workspace queries, mt_flash_attn_extend_kvq with its plan query, mt_kv_cache_append_quant
+// and mt_kv_cache_dequant. Kernels: fa_kvq.hip, fa_extend.hip.
 // Every argument is validated before the first device call.
 #include "../../include/minitorch_hip.h"
 #include "fa_kvq.h"
+#include "fa_extend.h"
 #include <math.h>
 
 namespace mt {
@@ -35,6 +37,15 @@ static int kvq_decode_sizes(int kv_dtype, int64_t B, int64_t H, int64_t Hkv, int
   if (B * H * Nq > (1ll << 31) - 1)
     return set_error("sizes out of range (B*H*Nq=%lld)", (long long)(B * H * Nq));
   return kvq_sizes(kv_dtype, B, Hkv, Nk, d);
+}
+
+// the extend step on a quantised cache: its format, mt_flash_attn_extend's sizes for fp32 rows and the
+// 8-element chunk rule on d
+static int kvq_extend_sizes(int kv_dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d) {
+  if (int rc = kvq_dtype(kv_dtype)) return rc;
+  if (int rc = extend_sizes(MT_F32, B, H, Hkv, Nq, Nk, d)) return rc;
+  if (d % 8) return set_error("a quantised cache needs rows of 8-element chunks: d=%lld is not a multiple of 8", (long long)d);
+  return 0;
 }
 
 // base pointer and every stride a multiple of `bytes` (strides in elements of esize bytes)
@@ -106,6 +117,40 @@ int mt_flash_attn_decode_kvq(int kv_dtype, int causal, const void* q, const void
   if (int rc = kvq_cache_aligned("v_cache", v_cache, a.vs, fp8)) return rc;
   if (int rc = kvq_aligned("o", o, a.os, 4, 16)) return rc;
   return check_hip(launch_decode_kvq(ka, fp8, B, (hipStream_t)stream), "mt_flash_attn_decode_kvq");
+}
+
+int mt_flash_attn_extend_kvq_plan(int kv_dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d,
+                                  int64_t* block_queries, int64_t* tile_keys) {
+  if (kvq_extend_sizes(kv_dtype, B, H, Hkv, Nq, Nk, d)) return -1;
+  const ExtendPlan p = extend_plan(4, d);  // the ring holds fp32 rows: the fp32 plan
+  if (block_queries) *block_queries = p.bq;
+  if (tile_keys) *tile_keys = p.bk;
+  return p.kernel;
+}
+
+int mt_flash_attn_extend_kvq(int kv_dtype, int causal, const void* q, const void* k_cache, const void* v_cache,
+                             const float* k_scale, const float* v_scale, void* o, float* m, float* l,
+                             int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t Nk, int64_t d,
+                             const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                             const int64_t* o_strides, const int* kv_len, const int* q_len, void* stream) {
+  if (int rc = kvq_extend_sizes(kv_dtype, B, H, Hkv, Nq, Nk, d)) return rc;
+  const bool fp8 = kv_dtype == MT_KV_FP8;
+  if (int rc = kvq_scales(fp8, k_scale, v_scale)) return rc;
+  KvqExtendArgs ka;
+  ExtendArgs& a = ka.e;
+  a.q = q; a.k = k_cache; a.v = v_cache; a.o = o;
+  strides_or_dense(a.qs, q_strides, H, Nq, d);
+  strides_or_dense(a.ks, k_strides, Hkv, Nk, d);
+  strides_or_dense(a.vs, v_strides, Hkv, Nk, d);
+  strides_or_dense(a.os, o_strides, H, Nq, d);
+  if (int rc = kvq_aligned("q", q, a.qs, 4, 16)) return rc;
+  if (int rc = kvq_cache_aligned("k_cache", k_cache, a.ks, fp8)) return rc;
+  if (int rc = kvq_cache_aligned("v_cache", v_cache, a.vs, fp8)) return rc;
+  if (int rc = kvq_aligned("o", o, a.os, 4, 16)) return rc;
+  extend_args(a, 4, causal, m, l, H, Hkv, Nq, Nk, d, kv_len, q_len);
+  a.o_f32 = 1;
+  ka.kscale = fp8 ? k_scale : nullptr; ka.vscale = fp8 ? v_scale : nullptr;
+  return check_hip(launch_extend_kvq(ka, fp8, B, (hipStream_t)stream), "mt_flash_attn_extend_kvq");
 }
 
 int mt_kv_cache_append_quant(int kv_dtype, const float* k_new, const float* v_new, void* k_cache, void* v_cache,

@@ -1,9 +1,11 @@
 // C ABI of the paged KV cache (include/minitorch_hip.h): mt_flash_attn_decode_paged with its
-// split / workspace queries, mt_kv_cache_append_paged and mt_kv_cache_gather_paged. Kernels:
-// fa_paged.hip. Every argument is validated before the first device call; the decode's sizes, strides and
-// alignment by the plain decode ABI's checks (capi_decode.hip, declared in fa_decode.h) at Nk = W * P.
+// split / workspace queries, mt_flash_attn_extend_paged with its plan query, mt_kv_cache_append_paged
+// and mt_kv_cache_gather_paged. Kernels: fa_paged.hip, fa_extend.hip. Every argument is validated
+// before the first device call; the decode's and the extend's sizes, strides and alignment by the
+// plain ABI's checks (capi_decode.hip, declared in fa_decode.h / fa_extend.h) at Nk = W * P.
 #include "../../include/minitorch_hip.h"
 #include "fa_paged.h"
+#include "fa_extend.h"
 #include <math.h>
 
 namespace mt {
@@ -98,6 +100,45 @@ int mt_flash_attn_decode_paged(int dtype, int causal, const void* q, const void*
   if (int rc = aligned16("o", o, a.os, osize)) return rc;
   pa.table = block_table; pa.W = (int)W; pa.lgP = lgP; pa.n_pages = (int)n_pages;
   return check_hip(launch_decode_paged(pa, esize == 2, B, (hipStream_t)stream), "mt_flash_attn_decode_paged");
+}
+
+int mt_flash_attn_extend_paged_plan(int dtype, int64_t B, int64_t H, int64_t Hkv, int64_t Nq, int64_t W, int64_t P,
+                                    int64_t d, int64_t* block_queries, int64_t* tile_keys) {
+  int lgP;
+  if (paged_geometry(W, P, 1, &lgP)) return -1;
+  if (extend_sizes(dtype, B, H, Hkv, Nq, W * P, d)) return -1;
+  const ExtendPlan p = extend_plan(dtype == MT_F32 ? 4 : 2, d);
+  if (block_queries) *block_queries = p.bq;
+  if (tile_keys) *tile_keys = p.bk;
+  return p.kernel;
+}
+
+int mt_flash_attn_extend_paged(int dtype, int causal, const void* q, const void* k_pool, const void* v_pool,
+                               void* o, float* m, float* l, int64_t B, int64_t H, int64_t Hkv, int64_t Nq,
+                               int64_t W, int64_t P, int64_t n_pages, int64_t d, const int64_t* q_strides,
+                               const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides,
+                               const int* block_table, const int* kv_len, const int* q_len, void* stream) {
+  int lgP;
+  if (int rc = paged_geometry(W, P, n_pages, &lgP)) return rc;
+  const int64_t Nk = W * P;
+  if (int rc = extend_sizes(dtype, B, H, Hkv, Nq, Nk, d)) return rc;
+  if (int rc = paged_table(block_table)) return rc;
+  const int esize = dtype == MT_F32 ? 4 : 2, osize = dtype == MT_BF16 ? 2 : 4;
+  PagedExtendArgs pa;
+  ExtendArgs& a = pa.e;
+  a.q = q; a.k = k_pool; a.v = v_pool; a.o = o;
+  strides_or_dense(a.qs, q_strides, H, Nq, d);
+  strides_or_dense(a.ks, k_strides, Hkv, P, d);
+  strides_or_dense(a.vs, v_strides, Hkv, P, d);
+  strides_or_dense(a.os, o_strides, H, Nq, d);
+  if (int rc = aligned16("q", q, a.qs, esize)) return rc;
+  if (int rc = aligned16("k_pool", k_pool, a.ks, esize)) return rc;
+  if (int rc = aligned16("v_pool", v_pool, a.vs, esize)) return rc;
+  if (int rc = aligned16("o", o, a.os, osize)) return rc;
+  extend_args(a, esize, causal, m, l, H, Hkv, Nq, Nk, d, kv_len, q_len);
+  a.o_f32 = osize == 4;
+  pa.table = block_table; pa.W = (int)W; pa.lgP = lgP; pa.n_pages = (int)n_pages;
+  return check_hip(launch_extend_paged(pa, esize == 2, B, (hipStream_t)stream), "mt_flash_attn_extend_paged");
 }
 
 int mt_kv_cache_append_paged(int dtype, const void* k_new, const void* v_new, void* k_pool, void* v_pool,

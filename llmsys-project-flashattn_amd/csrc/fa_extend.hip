@@ -22,14 +22,148 @@
 //    by a VALU fma, because the bf16 MFMA's accumulation rounds toward -inf (x3_tile_sum).
 //    fp32, 64 < d <= 256: the fp32 MFMA. bf16: the bf16 MFMA with P rounded to bf16.
 //  * int64 addressing; plain stores only; no workspace.
+//
+// Where the K / V rows live and what they are made of is the kernel's source, Src, in the spirit of
+// the decode kernel's (fa_decode_kernel.h). K and V enter the kernel in one place -- pre_load fetches
+// a tile's chunks into registers, pre_store puts them into the LDS ring -- and a source supplies only
+// what differs there, on two axes that compose:
+//   place   ExtContig / ExtPaged: the address of key row gr. A paged row goes through the block
+//           table entry of its own key, resolved per loaded row (a page may be smaller or larger
+//           than the tile), loaded under the row's predicate and clamped into [0, n_pages): no table
+//           entry at index >= ceil(n / P) and no pool row of a key >= the block's kend is read, and
+//           a table that breaks the contract reads a wrong page of the pool, never memory outside it
+//   format  ExtRows<T>: fp32 / bf16 rows in 16-B chunks, staged as they are. ExtQuant<KV>: bf16 /
+//           fp8 rows in 8-element chunks (kKvqEpc), kept as loaded until pre_store and widened there
+//           to fp32 with kvq_dequant's formulas (KV::unpack, for fp8 one fp32 product with the row's
+//           scale, loaded under the row's predicate), so the ring holds what it would hold after
+//           mt_kv_cache_dequant and the kernel is the fp32 one from there on
+// Everything after the ring -- limits, masks, X3 planes, MFMA order, online softmax, epilogue -- is
+// below, once: the same bits for the same rows however they are stored. Instantiated: ExtPlainSrc<T>
+// (contiguous rows: mt_flash_attn_extend), ExtPagedSrc<T> (mt_flash_attn_extend_paged) and
+// ExtKvqSrc<KV> (mt_flash_attn_extend_kvq); a paged and quantised source would be a fourth.
+// Resources of every instantiation: profiles/extend_kernels_resources.txt.
 #include <type_traits>
 
 #include "fa_extend.h"
+#include "fa_kvq.h"
 
 namespace mt {
 
-template <typename T, int DT, int DV, int KB, bool X3, int MINB>
-__global__ __launch_bounds__(256, MINB) void fa_extend_ring(ExtendArgs p) {
+// ---- place: the address of a key row ------------------------------------------------------------
+// Row: what row(gr, live) resolves for key gr (live: the row may be read) ahead of the tile's loads;
+// head(p, b, hkv, s): this kv head's rows (of page 0); at(base, s, gr, row): the row's first element
+struct ExtContig {
+  using Row = int;
+  template <typename E>
+  static __device__ __forceinline__ const E* head(const E* p, int b, int hkv, const int64_t* s) {
+    return p + b * s[0] + hkv * s[1];
+  }
+  __device__ __forceinline__ Row row(int gr, bool) const { return gr; }
+  template <typename E>
+  __device__ __forceinline__ const E* at(const E* base, const int64_t* s, int gr, Row) const {
+    return base + (int64_t)gr * s[2];
+  }
+};
+struct ExtPaged {
+  using Row = int;  // the page
+  const int* tb;    // this batch row's table entries
+  int lgP, pmask, pmax;
+  template <typename E>
+  static __device__ __forceinline__ const E* head(const E* p, int, int hkv, const int64_t* s) { return p + hkv * s[1]; }
+  __device__ __forceinline__ Row row(int gr, bool live) const {
+    int pg = 0;
+    if (live) pg = (int)min((unsigned)tb[gr >> lgP], (unsigned)pmax);  // a negative entry: the last page
+    return pg;
+  }
+  template <typename E>
+  __device__ __forceinline__ const E* at(const E* base, const int64_t* s, int gr, Row pg) const {
+    return base + (int64_t)pg * s[0] + (int64_t)(gr & pmask) * s[2];
+  }
+};
+
+// ---- format: what a row is made of ----------------------------------------------------------------
+// T: the element type of Q and of the ring; E: a storage element (the unit of ks / vs); Raw: a chunk
+// of EPC elements as loaded; stage(): the 16-B ring chunks (EPC * sizeof(T) / 16 of them) it becomes
+template <typename T_> struct ExtRows {
+  using T = T_;
+  using E = T_;
+  using Raw = uint4;
+  static constexpr int EPC = 16 / sizeof(T_);
+  static constexpr bool kScaled = false;
+  static __device__ __forceinline__ Raw zero() { return make_uint4(0, 0, 0, 0); }
+  static __device__ __forceinline__ void stage(const Raw& u, float, uint4* out) { out[0] = u; }
+};
+template <typename KV> struct ExtQuant {
+  using T = float;
+  using E = typename std::conditional<KV::kBytes == 2, bf16, unsigned char>::type;
+  using Raw = typename KV::Raw;
+  static constexpr int EPC = kKvqEpc;
+  static constexpr bool kScaled = KV::kScaled;
+  static __device__ __forceinline__ Raw zero() { return KV::zero(); }
+  static __device__ __forceinline__ void stage(const Raw& u, float s, uint4* out) {
+    float f[kKvqEpc];
+    KV::unpack(u, f);
+    if constexpr (KV::kScaled) {
+      // the product is rounded to fp32 here, as kvq_dequant stores it: the empty asm keeps the X3 split
+      // behind it (x - top half of x) from contracting it into an fma on the unrounded product
+#pragma unroll
+      for (int e = 0; e < kKvqEpc; ++e) {
+        f[e] *= s;
+        asm("" : "+v"(f[e]));
+      }
+    }
+    out[0] = __builtin_bit_cast(uint4, make_float4(f[0], f[1], f[2], f[3]));
+    out[1] = __builtin_bit_cast(uint4, make_float4(f[4], f[5], f[6], f[7]));
+  }
+};
+
+// ---- the instantiated sources ---------------------------------------------------------------------
+// Args, base(args): the kernel's argument struct and the ExtendArgs in it; place; scale(which, gr):
+// the fp32 scale of K (0) / V (1) row gr, for a scaled format; kPlain: contiguous rows staged as loaded.
+// For kPlain, pre_load and pre_store keep the statements the kernel had before it took a source instead
+// of going through place / stage: the same arithmetic either way, but through the general path the eight
+// plain kernels came out with another instruction order (same counts, registers and occupancy) and ran
+// 1-1.5 % slower at fp32 d = 64 and bf16 d = 128; spelled this way their device code is the earlier
+// kernel's instruction for instruction
+template <typename T> struct ExtPlainSrc : ExtRows<T> {
+  using Args = ExtendArgs;
+  static constexpr bool kPlain = true;
+  static __host__ __device__ __forceinline__ const ExtendArgs& base(const Args& sa) { return sa; }
+  ExtContig place;
+  __device__ __forceinline__ ExtPlainSrc(const Args&, int, int) {}
+  __device__ __forceinline__ float scale(int, int) const { return 0.f; }
+};
+template <typename T> struct ExtPagedSrc : ExtRows<T> {
+  using Args = PagedExtendArgs;
+  static constexpr bool kPlain = false;
+  static __host__ __device__ __forceinline__ const ExtendArgs& base(const Args& sa) { return sa.e; }
+  ExtPaged place;
+  __device__ __forceinline__ ExtPagedSrc(const Args& sa, int b, int)
+      : place{sa.table + (int64_t)b * sa.W, sa.lgP, (1 << sa.lgP) - 1, sa.n_pages - 1} {}
+  __device__ __forceinline__ float scale(int, int) const { return 0.f; }
+};
+template <typename KV> struct ExtKvqSrc : ExtQuant<KV> {
+  using Args = KvqExtendArgs;
+  static constexpr bool kPlain = false;
+  static __host__ __device__ __forceinline__ const ExtendArgs& base(const Args& sa) { return sa.e; }
+  ExtContig place;
+  const float* sc[2];  // this (b, hkv)'s row scales
+  __device__ __forceinline__ ExtKvqSrc(const Args& sa, int b, int hkv)
+      : sc{nullptr, nullptr} {
+    if constexpr (KV::kScaled) {  // an unscaled format has no scale arrays (NULL)
+      sc[0] = sa.kscale + ((int64_t)b * sa.e.Hkv + hkv) * sa.e.Nk;
+      sc[1] = sa.vscale + ((int64_t)b * sa.e.Hkv + hkv) * sa.e.Nk;
+    }
+  }
+  __device__ __forceinline__ float scale(int which, int gr) const { return sc[which][gr]; }
+};
+
+template <typename Src, int DT, int DV, int KB, bool X3, int MINB>
+__global__ __launch_bounds__(256, MINB) void fa_extend_ring(const typename Src::Args sa) {
+  using T = typename Src::T;
+  using E = typename Src::E;
+  using Raw = typename Src::Raw;
+  const ExtendArgs& p = Src::base(sa);
   static_assert(!X3 || std::is_same<T, float>::value, "x3: fp32 inputs");
   static_assert(DT % DV == 0 && (!X3 || DV == DT), "O column slices");
   constexpr int BQ = 128, BK = 32 * KB;
@@ -59,10 +193,17 @@ __global__ __launch_bounds__(256, MINB) void fa_extend_ring(ExtendArgs p) {
   }
   const int b = bh / p.H, hh = bh % p.H, hkv = hh / (p.H / p.Hkv);
   const T* Qg = (const T*)p.q + b * p.qs[0] + hh * p.qs[1];
-  const T* Kg = (const T*)p.k + b * p.ks[0] + hkv * p.ks[1];
-  const T* Vg = (const T*)p.v + b * p.vs[0] + hkv * p.vs[1];
-  constexpr int EPC = 16 / sizeof(T), CPR = DT / EPC, NCK = BK * CPR / 256;
-  constexpr int CPV = DV / EPC, NCV = BK * CPV / 256;
+  const Src src(sa, b, hkv);
+  const E* Kg = src.place.head((const E*)p.k, b, hkv, p.ks);
+  const E* Vg = src.place.head((const E*)p.v, b, hkv, p.vs);
+  constexpr int EPC = 16 / sizeof(T);  // elements of a 16-B chunk of Q and of the ring
+  // K / V chunks as the source loads them: SPC elements, SUB ring chunks each; a thread takes NCK of K
+  // and NCV of V per tile (ALLK / ALLV: every thread has a chunk in each round)
+  constexpr int SPC = Src::EPC, SUB = SPC / EPC;
+  constexpr int CPR = DT / SPC, NCK = BK * CPR >= 256 ? BK * CPR / 256 : 1;
+  constexpr int CPV = DV / SPC, NCV = BK * CPV >= 256 ? BK * CPV / 256 : 1;
+  constexpr bool ALLK = BK * CPR >= 256, ALLV = BK * CPV >= 256;
+  using Row = typename decltype(src.place)::Row;
 
   // n keys held, t real queries: query i < t sits at position n - t + i
   const int n = p.kv_len ? max(0, min(p.Nk, p.kv_len[b])) : p.Nk;
@@ -109,23 +250,59 @@ __global__ __launch_bounds__(256, MINB) void fa_extend_ring(ExtendArgs p) {
 
   const int ntiles = (kend + BK - 1) / BK;
 
-  uint4 pk[NCK], pv[NCV];
+  Raw pk[NCK], pv[NCV];
+  float sk[Src::kScaled ? NCK : 1], sv[Src::kScaled ? NCV : 1];  // row scales: gone unless Src::kScaled
   auto pre_load = [&](int k0) __attribute__((always_inline)) {
+    if constexpr (Src::kPlain) {  // see kPlain above
 #pragma unroll
-    for (int i = 0; i < NCK; ++i) {
-      const int ch = tid + 256 * i, r = ch / CPR, cc = (ch % CPR) * EPC, gr = k0 + r;
-      pk[i] = make_uint4(0, 0, 0, 0);
-      if (gr < kend && cc < d) pk[i] = *(const uint4*)(Kg + (int64_t)gr * p.ks[2] + cc);
-    }
+      for (int i = 0; i < NCK; ++i) {
+        const int ch = tid + 256 * i, r = ch / CPR, cc = (ch % CPR) * EPC, gr = k0 + r;
+        pk[i] = make_uint4(0, 0, 0, 0);
+        if (gr < kend && cc < d) pk[i] = *(const uint4*)(Kg + (int64_t)gr * p.ks[2] + cc);
+      }
 #pragma unroll
-    for (int i = 0; i < NCV; ++i) {
-      const int ch = tid + 256 * i, r = ch / CPV, cc = oc + (ch % CPV) * EPC, gr = k0 + r;
-      pv[i] = make_uint4(0, 0, 0, 0);
-      if (gr < kend && cc < d) pv[i] = *(const uint4*)(Vg + (int64_t)gr * p.vs[2] + cc);
+      for (int i = 0; i < NCV; ++i) {
+        const int ch = tid + 256 * i, r = ch / CPV, cc = oc + (ch % CPV) * EPC, gr = k0 + r;
+        pv[i] = make_uint4(0, 0, 0, 0);
+        if (gr < kend && cc < d) pv[i] = *(const uint4*)(Vg + (int64_t)gr * p.vs[2] + cc);
+      }
+    } else {
+      // the rows of the tile first (a paged source: its table entries), then their chunks
+      Row rk[NCK], rv[NCV];
+#pragma unroll
+      for (int i = 0; i < NCK; ++i) {
+        const int ch = tid + 256 * i, gr = k0 + ch / CPR;
+        rk[i] = src.place.row(gr, (ALLK || ch < BK * CPR) && gr < kend);
+      }
+#pragma unroll
+      for (int i = 0; i < NCV; ++i) {
+        const int ch = tid + 256 * i, gr = k0 + ch / CPV;
+        rv[i] = CPV == CPR ? rk[i] : src.place.row(gr, (ALLV || ch < BK * CPV) && gr < kend);
+      }
+#pragma unroll
+      for (int i = 0; i < NCK; ++i) {
+        const int ch = tid + 256 * i, r = ch / CPR, cc = (ch % CPR) * SPC, gr = k0 + r;
+        pk[i] = Src::zero();
+        if constexpr (Src::kScaled) sk[i] = 0.f;
+        if ((ALLK || ch < BK * CPR) && gr < kend && cc < d) {
+          pk[i] = *(const Raw*)(src.place.at(Kg, p.ks, gr, rk[i]) + cc);
+          if constexpr (Src::kScaled) sk[i] = src.scale(0, gr);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < NCV; ++i) {
+        const int ch = tid + 256 * i, r = ch / CPV, cc = oc + (ch % CPV) * SPC, gr = k0 + r;
+        pv[i] = Src::zero();
+        if constexpr (Src::kScaled) sv[i] = 0.f;
+        if ((ALLV || ch < BK * CPV) && gr < kend && cc < d) {
+          pv[i] = *(const Raw*)(src.place.at(Vg, p.vs, gr, rv[i]) + cc);
+          if constexpr (Src::kScaled) sv[i] = src.scale(1, gr);
+        }
+      }
     }
   };
   auto pre_store = [&](int s) __attribute__((always_inline)) {
-    if constexpr (X3) {  // three bf16 planes per tensor: 8 B of each per 16-B chunk
+    if constexpr (Src::kPlain && X3) {  // see kPlain above
       bf16* sl = ring3 + s * 6 * PLANE;
 #pragma unroll
       for (int i = 0; i < NCK; ++i) {
@@ -135,17 +312,60 @@ __global__ __launch_bounds__(256, MINB) void fa_extend_ring(ExtendArgs p) {
       }
       return;
     }
+    if constexpr (Src::kPlain) {
+      T* sK = ring + s * SLOT;
+      T* sV = sK + BK * LD;
+#pragma unroll
+      for (int i = 0; i < NCK; ++i) {
+        const int ch = tid + 256 * i, r = ch / CPR, cc = (ch % CPR) * EPC;
+        *(uint4*)(sK + r * LD + cc) = pk[i];
+      }
+#pragma unroll
+      for (int i = 0; i < NCV; ++i) {
+        const int ch = tid + 256 * i, r = ch / CPV, cc = (ch % CPV) * EPC;
+        *(uint4*)(sV + r * LDV + cc) = pv[i];
+      }
+      return;
+    }
+    if constexpr (X3) {  // three bf16 planes per tensor: 8 B of each per 16-B chunk
+      bf16* sl = ring3 + s * 6 * PLANE;
+#pragma unroll
+      for (int i = 0; i < NCK; ++i) {
+        const int ch = tid + 256 * i, r = ch / CPR, cc = (ch % CPR) * SPC;
+        uint4 ck[SUB], cv[SUB];
+        Src::stage(pk[i], sk[Src::kScaled ? i : 0], ck);
+        Src::stage(pv[i], sv[Src::kScaled ? i : 0], cv);
+        if (ALLK || ch < BK * CPR) {
+#pragma unroll
+          for (int j = 0; j < SUB; ++j) {
+            x3_store4(sl + r * LDB + cc + j * EPC, PLANE, ck[j]);
+            x3_store4(sl + 3 * PLANE + r * LDB + cc + j * EPC, PLANE, cv[j]);
+          }
+        }
+      }
+      return;
+    }
     T* sK = ring + s * SLOT;
     T* sV = sK + BK * LD;
 #pragma unroll
     for (int i = 0; i < NCK; ++i) {
-      const int ch = tid + 256 * i, r = ch / CPR, cc = (ch % CPR) * EPC;
-      *(uint4*)(sK + r * LD + cc) = pk[i];
+      const int ch = tid + 256 * i, r = ch / CPR, cc = (ch % CPR) * SPC;
+      uint4 c[SUB];
+      Src::stage(pk[i], sk[Src::kScaled ? i : 0], c);
+      if (ALLK || ch < BK * CPR) {
+#pragma unroll
+        for (int j = 0; j < SUB; ++j) *(uint4*)(sK + r * LD + cc + j * EPC) = c[j];
+      }
     }
 #pragma unroll
     for (int i = 0; i < NCV; ++i) {
-      const int ch = tid + 256 * i, r = ch / CPV, cc = (ch % CPV) * EPC;
-      *(uint4*)(sV + r * LDV + cc) = pv[i];
+      const int ch = tid + 256 * i, r = ch / CPV, cc = (ch % CPV) * SPC;
+      uint4 c[SUB];
+      Src::stage(pv[i], sv[Src::kScaled ? i : 0], c);
+      if (ALLV || ch < BK * CPV) {
+#pragma unroll
+        for (int j = 0; j < SUB; ++j) *(uint4*)(sV + r * LDV + cc + j * EPC) = c[j];
+      }
     }
   };
   if (ntiles > 0) {
@@ -283,17 +503,19 @@ __global__ __launch_bounds__(256, MINB) void fa_extend_ring(ExtendArgs p) {
   }
 }
 
-template <typename T, int DT, int DV, int KB, bool X3, int MINB>
-static hipError_t launch_extend_t(const ExtendArgs& a, int64_t B, hipStream_t st) {
+template <typename Src, int DT, int DV, int KB, bool X3, int MINB>
+static hipError_t launch_extend_t(const typename Src::Args& sa, int64_t B, hipStream_t st) {
+  using T = typename Src::T;
+  const ExtendArgs& a = Src::base(sa);
   // two slots of K and V: fp32 / bf16 rows, or (X3) three bf16 planes each
   const size_t smem = X3 ? (size_t)2 * 6 * 32 * KB * (DT + 8) * 2
                          : sizeof(T) * (size_t)(DT + DV + 32 / sizeof(T)) * 2 * 32 * KB;
-  auto kfn = fa_extend_ring<T, DT, DV, KB, X3, MINB>;
+  auto kfn = fa_extend_ring<Src, DT, DV, KB, X3, MINB>;
   hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)smem);
   if (e != hipSuccess) return e;
   dim3 grid((unsigned)(a.nqb * B * a.H * (DT / DV)), 1, 1);
-  hipLaunchKernelGGL(kfn, grid, dim3(256), smem, st, a);
+  hipLaunchKernelGGL(kfn, grid, dim3(256), smem, st, sa);
   return hipGetLastError();
 }
 
@@ -313,17 +535,36 @@ ExtendPlan extend_plan(int esize, int64_t d) {
   return {7, 128, 32};
 }
 
-hipError_t launch_extend(const ExtendArgs& a, bool bf16_in, int64_t B, hipStream_t st) {
-  switch (extend_plan(bf16_in ? 2 : 4, a.d).kernel) {
-    case 0: return launch_extend_t<float, 32, 32, 1, true, 2>(a, B, st);
-    case 1: return launch_extend_t<float, 64, 64, 1, true, 2>(a, B, st);
-    case 2: return launch_extend_t<float, 128, 128, 1, false, 2>(a, B, st);
-    case 3: return launch_extend_t<float, 256, 128, 1, false, 1>(a, B, st);
-    case 4: return launch_extend_t<bf16, 32, 32, 2, false, 2>(a, B, st);
-    case 5: return launch_extend_t<bf16, 64, 64, 2, false, 2>(a, B, st);
-    case 6: return launch_extend_t<bf16, 128, 128, 2, false, 2>(a, B, st);
-    default: return launch_extend_t<bf16, 256, 256, 1, false, 1>(a, B, st);
+// the fp32 plan's instantiations (ids 0-3) on a source with fp32 Q, the bf16 plan's (4-7) on a bf16 one
+template <typename Src>
+static hipError_t launch_extend_f32(const typename Src::Args& sa, int64_t B, hipStream_t st) {
+  switch (extend_plan(4, Src::base(sa).d).kernel) {
+    case 0: return launch_extend_t<Src, 32, 32, 1, true, 2>(sa, B, st);
+    case 1: return launch_extend_t<Src, 64, 64, 1, true, 2>(sa, B, st);
+    case 2: return launch_extend_t<Src, 128, 128, 1, false, 2>(sa, B, st);
+    default: return launch_extend_t<Src, 256, 128, 1, false, 1>(sa, B, st);
   }
+}
+template <typename Src>
+static hipError_t launch_extend_bf16(const typename Src::Args& sa, int64_t B, hipStream_t st) {
+  switch (extend_plan(2, Src::base(sa).d).kernel) {
+    case 4: return launch_extend_t<Src, 32, 32, 2, false, 2>(sa, B, st);
+    case 5: return launch_extend_t<Src, 64, 64, 2, false, 2>(sa, B, st);
+    case 6: return launch_extend_t<Src, 128, 128, 2, false, 2>(sa, B, st);
+    default: return launch_extend_t<Src, 256, 256, 1, false, 1>(sa, B, st);
+  }
+}
+
+hipError_t launch_extend(const ExtendArgs& a, bool bf16_in, int64_t B, hipStream_t st) {
+  return bf16_in ? launch_extend_bf16<ExtPlainSrc<bf16>>(a, B, st) : launch_extend_f32<ExtPlainSrc<float>>(a, B, st);
+}
+
+hipError_t launch_extend_paged(const PagedExtendArgs& a, bool bf16_in, int64_t B, hipStream_t st) {
+  return bf16_in ? launch_extend_bf16<ExtPagedSrc<bf16>>(a, B, st) : launch_extend_f32<ExtPagedSrc<float>>(a, B, st);
+}
+
+hipError_t launch_extend_kvq(const KvqExtendArgs& a, bool fp8, int64_t B, hipStream_t st) {
+  return fp8 ? launch_extend_f32<ExtKvqSrc<KvFp8>>(a, B, st) : launch_extend_f32<ExtKvqSrc<KvBf16>>(a, B, st);
 }
 
 }  // namespace mt

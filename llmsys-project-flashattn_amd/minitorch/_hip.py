@@ -27,6 +27,7 @@ MT_KV_BF16 = 1
 MT_KV_FP8 = 2
 
 _lib = None
+_allow_missing = False  # use_library(path, allow_missing=True): an older build may lack the newest entry points
 
 _i64 = ctypes.c_int64
 _int = ctypes.c_int
@@ -72,6 +73,9 @@ _PROTOS = {
     "mt_flash_attn_decode_kvq_workspace_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64, _i64]),
     "mt_flash_attn_decode_kvq": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64,
                                         _i64, _i64, _i64p, _i64p, _i64p, _i64p, _vp, _vp, _i64, _vp]),
+    "mt_flash_attn_extend_kvq_plan": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64p, _i64p]),
+    "mt_flash_attn_extend_kvq": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64,
+                                        _i64, _i64, _i64p, _i64p, _i64p, _i64p, _vp, _vp, _vp]),
     "mt_kv_cache_append_quant": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                         _i64p, _i64p, _i64p, _i64p, _vp, _vp]),
     "mt_kv_cache_dequant": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64,
@@ -80,6 +84,9 @@ _PROTOS = {
     "mt_flash_attn_decode_paged_workspace_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64]),
     "mt_flash_attn_decode_paged": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                           _i64, _i64, _i64, _i64p, _i64p, _i64p, _i64p, _vp, _vp, _vp, _i64, _vp]),
+    "mt_flash_attn_extend_paged_plan": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64p, _i64p]),
+    "mt_flash_attn_extend_paged": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                          _i64, _i64, _i64, _i64p, _i64p, _i64p, _i64p, _vp, _vp, _vp, _vp]),
     "mt_kv_cache_append_paged": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                         _i64p, _i64p, _i64p, _i64p, _vp, _vp, _vp, _vp]),
     "mt_kv_cache_gather_paged": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -148,7 +155,11 @@ def lib() -> ctypes.CDLL:
             pass
         l = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in _PROTOS.items():
-            fn = getattr(l, name)
+            fn = getattr(l, name, None)
+            if fn is None:
+                if _allow_missing:
+                    continue
+                raise AttributeError(f"{LIB_PATH} lacks {name}: rebuild it")
             fn.restype = res
             fn.argtypes = args
         _lib = l
@@ -173,14 +184,16 @@ def _bind_fast(l: ctypes.CDLL) -> None:
     fast = _mtfast
 
 
-def use_library(path: str) -> ctypes.CDLL:
+def use_library(path: str, allow_missing: bool = False) -> ctypes.CDLL:
     """Load a different build of the library (diagnostics only: scripts/ablate*.py load
     ``_lib/diag/libminitorch_hip_diag.so``, built by ``make DIAG=1``). The package itself
-    always loads LIB_PATH."""
-    global _lib, LIB_PATH
+    always loads LIB_PATH. allow_missing: an entry point the build lacks (an older build, for an
+    A/B against it) is left unbound, ``hasattr(lib(), name)`` tells, instead of being an error."""
+    global _lib, LIB_PATH, _allow_missing
     if _lib is not None:
         raise RuntimeError("use_library() must run before the first lib() call")
     LIB_PATH = path
+    _allow_missing = bool(allow_missing)
     return lib()
 
 
@@ -591,6 +604,50 @@ def flash_decode_kvq(q, k_cache, v_cache, k_scale=None, v_scale=None, kv_len=Non
     return out, m, l
 
 
+def extend_kvq_plan(kv_dtype: int, B: int, H: int, Nq: int, Nk: int, d: int, Hkv: Optional[int] = None):
+    """(kernel id, block_queries, tile_keys) of mt_flash_attn_extend_kvq: extend_plan's answer for
+    MT_F32 at the same sizes, whatever the format (the rows are staged as fp32)."""
+    bq, bk = ctypes.c_int64(0), ctypes.c_int64(0)
+    kid = lib().mt_flash_attn_extend_kvq_plan(kv_dtype, B, H, H if Hkv is None else Hkv, Nq, Nk, d,
+                                              ctypes.byref(bq), ctypes.byref(bk))
+    if kid < 0:
+        raise ValueError(lib().mt_last_error().decode(errors="replace"))
+    return kid, bq.value, bk.value
+
+
+def flash_extend_kvq(q, k_cache, v_cache, k_scale=None, v_scale=None, kv_len=None, q_len=None, causal: bool = True,
+                     out=None, m=None, l=None, stream: Optional[int] = None):
+    """Extend attention on a quantised cache read in place (mt_flash_attn_extend_kvq): flash_extend's
+    contract with an fp32 q [B,H,Nq,d], fp32 (O, m, l) and the caches [B,Hkv,Nk,d] as torch.bfloat16,
+    or torch.uint8 e4m3 codes with the fp32 row scales [B,Hkv,Nk]. The bits are those of
+    kv_cache_dequant followed by flash_extend. One launch, no workspace."""
+    torch = _torch()
+    _check_dev(q, k_cache, v_cache)
+    B, H, Nq, d = q.shape
+    if q.dtype != torch.float32:
+        raise TypeError("flash_extend_kvq takes float32 queries")
+    code, Hkv, Nk, ksp, vsp = _kvq_caches("flash_extend_kvq", k_cache, v_cache, k_scale, v_scale, B, d)
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"the caches' {Hkv} heads do not divide q's {H} heads")
+    if out is None:
+        out = torch.empty((B, H, Nq, d), dtype=torch.float32, device=q.device)
+    elif out.dtype != torch.float32:
+        raise TypeError("flash_extend_kvq writes a float32 O")
+    if m is None:
+        m = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    if l is None:
+        l = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    kv = _kv_arg(kv_len, B, q.device)
+    ql = _kv_arg(q_len, B, q.device)
+    st = stream_ptr(q.device) if stream is None else stream
+    check(lib().mt_flash_attn_extend_kvq(
+        code, int(causal), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), ksp, vsp, out.data_ptr(),
+        m.data_ptr(), l.data_ptr(), B, H, Hkv, Nq, Nk, d, strides3(q), strides3(k_cache), strides3(v_cache),
+        strides3(out), None if kv is None else kv.data_ptr(), None if ql is None else ql.data_ptr(), st),
+        "mt_flash_attn_extend_kvq")
+    return out, m, l
+
+
 def kv_cache_dequant(k_cache, v_cache, k_scale=None, v_scale=None, kv_len=None, k_out=None, v_out=None,
                      stream: Optional[int] = None):
     """The fp32 values of the first kv_len[b] rows (None: all) of a quantised cache
@@ -687,6 +744,54 @@ def flash_decode_paged(q, k_pool, v_pool, block_table, kv_len=None, causal: bool
         None if workspace is None else workspace.data_ptr(),
         0 if workspace is None else workspace.numel() * workspace.element_size(), st),
         "mt_flash_attn_decode_paged")
+    return out, m, l
+
+
+def extend_paged_plan(dtype: int, B: int, H: int, Nq: int, W: int, P: int, d: int, Hkv: Optional[int] = None):
+    """(kernel id, block_queries, tile_keys) of mt_flash_attn_extend_paged: extend_plan's answer at
+    Nk = W * P. A function of the sizes only."""
+    bq, bk = ctypes.c_int64(0), ctypes.c_int64(0)
+    kid = lib().mt_flash_attn_extend_paged_plan(dtype, B, H, H if Hkv is None else Hkv, Nq, W, P, d,
+                                                ctypes.byref(bq), ctypes.byref(bk))
+    if kid < 0:
+        raise ValueError(lib().mt_last_error().decode(errors="replace"))
+    return kid, bq.value, bk.value
+
+
+def flash_extend_paged(q, k_pool, v_pool, block_table, kv_len=None, q_len=None, causal: bool = True, out=None,
+                       m=None, l=None, out_dtype=None, stream: Optional[int] = None):
+    """Extend attention on a paged cache read in place (mt_flash_attn_extend_paged): flash_extend's
+    contract with q [B,H,Nq,d] against the page pools [n_pages,Hkv,P,d] (any strides with unit-stride
+    d) through block_table (device int32 [B,W]: key j of row b is row j % P of page
+    block_table[b, j // P]). The first kv_len[b] of the W * P logical keys are visible (None: all).
+    The bits are those of flash_extend on a contiguous cache holding the same rows. Returns (O, m, l).
+    One launch, no workspace."""
+    torch = _torch()
+    _check_dev(q)
+    B, H, Nq, d = q.shape
+    n_pages, Hkv, P, dp, W = _paged_pools("flash_extend_paged", k_pool, v_pool, block_table, B)
+    if dp != d:
+        raise ValueError(f"pool shape {tuple(k_pool.shape)} does not match q {tuple(q.shape)}")
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"the pools' {Hkv} heads do not divide q's {H} heads")
+    if not (q.dtype == k_pool.dtype == v_pool.dtype):
+        raise TypeError("q/k_pool/v_pool dtypes differ")
+    code = _decode_code(q, out, out_dtype)
+    if out is None:
+        out = torch.empty((B, H, Nq, d), dtype=torch.float32 if code == 2 else q.dtype, device=q.device)
+    if m is None:
+        m = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    if l is None:
+        l = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    kv = _kv_arg(kv_len, B, q.device)
+    ql = _kv_arg(q_len, B, q.device)
+    st = stream_ptr(q.device) if stream is None else stream
+    check(lib().mt_flash_attn_extend_paged(
+        code, int(causal), q.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), out.data_ptr(),
+        m.data_ptr(), l.data_ptr(), B, H, Hkv, Nq, W, P, n_pages, d, strides3(q), strides3(k_pool),
+        strides3(v_pool), strides3(out), block_table.data_ptr(), None if kv is None else kv.data_ptr(),
+        None if ql is None else ql.data_ptr(), st),
+        "mt_flash_attn_extend_paged")
     return out, m, l
 
 

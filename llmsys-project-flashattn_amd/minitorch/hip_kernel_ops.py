@@ -566,6 +566,22 @@ class HipKernelOps(TensorOps):
         return _wrap(o, (B, H, Nq, d), Q.backend, so)
 
     @staticmethod
+    def flash_attention_extend_kvq(Q: Tensor, kc, vc, k_scale=None, v_scale=None, kv_len=None, q_len=None,
+                                   causal: bool = True) -> Tensor:
+        """flash_attention_extend on a quantised cache read in place (mt_flash_attn_extend_kvq): fp32
+        Q and O, the torch caches kc / vc [B,Hkv,Nmax,d] in bf16 or e4m3 codes with their row
+        scales. The bits of kv_cache_dequant followed by flash_attention_extend."""
+        import torch
+        B, H, Nq, d = Q.shape
+        so = _layout_like(Q)
+        o = torch.empty(B * H * Nq * d, dtype=torch.float32, device="cuda")
+        _hip.flash_extend_kvq(_torch_view(Q), kc, vc, k_scale, v_scale,
+                              kv_len=None if kv_len is None else HipKernelOps._i32(kv_len),
+                              q_len=None if q_len is None else HipKernelOps._i32(q_len), causal=causal,
+                              out=torch.as_strided(o, (B, H, Nq, d), so))
+        return _wrap(o, (B, H, Nq, d), Q.backend, so)
+
+    @staticmethod
     def kv_cache_dequant(kc, vc, k_scale, v_scale, kv_len, Kout: Tensor, Vout: Tensor) -> None:
         """The fp32 values of the first kv_len[b] rows of the quantised torch caches written into
         the fp32 tensors Kout / Vout [B,Hkv,Nmax,d] (mt_kv_cache_dequant)."""
@@ -595,6 +611,22 @@ class HipKernelOps(TensorOps):
         _hip.flash_decode_paged(_torch_view(Q), kp, vp, block_table,
                                 kv_len=None if kv_len is None else HipKernelOps._i32(kv_len), causal=causal,
                                 out=torch.as_strided(o, (B, H, Nq, d), so), workspace=workspace)
+        return _wrap(o, (B, H, Nq, d), Q.backend, so)
+
+    @staticmethod
+    def flash_attention_extend_paged(Q: Tensor, kp, vp, block_table, kv_len=None, q_len=None,
+                                     causal: bool = True) -> Tensor:
+        """flash_attention_extend on a paged cache read in place (mt_flash_attn_extend_paged): the page
+        pools kp / vp [n_pages,Hkv,P,d] read through block_table [B,W]. The bits of
+        flash_attention_extend on a contiguous cache holding the same rows."""
+        import torch
+        B, H, Nq, d = Q.shape
+        so = _layout_like(Q)
+        o = torch.empty(B * H * Nq * d, dtype=torch.float32, device="cuda")
+        _hip.flash_extend_paged(_torch_view(Q), kp, vp, block_table,
+                                kv_len=None if kv_len is None else HipKernelOps._i32(kv_len),
+                                q_len=None if q_len is None else HipKernelOps._i32(q_len), causal=causal,
+                                out=torch.as_strided(o, (B, H, Nq, d), so))
         return _wrap(o, (B, H, Nq, d), Q.backend, so)
 
     @staticmethod

@@ -12,8 +12,8 @@ conversation, a chunk of a long prompt; ``extend_counts`` builds that step's cou
 ``kv_dtype="bf16"`` / ``"fp8"`` stores K and V quantised (torch.bfloat16, or torch.uint8 holding
 OCP e4m3 codes with one fp32 scale per cached row): the new rows are quantised as they are appended
 (``mt_kv_cache_append_quant``), a decode step reads the quantised rows directly
-(``mt_flash_attn_decode_kvq``) and an extend step dequantises the visible rows into one fp32
-scratch pair shared by the layers (``mt_kv_cache_dequant``) for the fp32 extend kernel.
+(``mt_flash_attn_decode_kvq``) and so does an extend step (``mt_flash_attn_extend_kvq``, which
+widens the rows as it stages them): no fp32 copy of the cache exists.
 
 ``PagedKVCache`` keeps the rows in pages of a pool instead, addressed through a block table
 (``PageAllocator`` is its host-side free list with reference counts): memory follows the tokens
@@ -56,7 +56,7 @@ class KVCache:
         self.quantised = self.kv_dtype != "fp32"
         if self.quantised:
             if any(getattr(backend, f, None) is None
-                   for f in ("kv_cache_append_quant", "flash_attention_decode_kvq", "kv_cache_dequant")):
+                   for f in ("kv_cache_append_quant", "flash_attention_decode_kvq", "flash_attention_extend_kvq")):
                 raise ValueError("KVCache(kv_dtype=...) needs a backend with the quantised-cache kernels (HipKernelOps)")
             if head_dim % 8 != 0:
                 raise ValueError(f"KVCache: a quantised cache needs head_dim % 8 == 0, got {head_dim}")
@@ -79,7 +79,7 @@ class KVCache:
         strides = (n_positions * n_kv_head * head_dim, head_dim, n_kv_head * head_dim, 1)
         numel = batch_size * n_positions * n_kv_head * head_dim
 
-        self._shape, self._strides, self._numel = shape, strides, numel
+        self._numel = numel
 
         def buf():
             return Tensor(TensorData(torch.empty(numel, dtype=torch.float32, device="cuda"), shape, strides),
@@ -97,7 +97,6 @@ class KVCache:
             self.layers = [LayerKV(self, qbuf(), qbuf(), sbuf(), sbuf()) for _ in range(n_layer)]
         else:
             self.layers = [LayerKV(self, buf(), buf()) for _ in range(n_layer)]
-        self._scratch = None      # quantised: the fp32 K / V pair of one layer's size for extend steps
         self._workspaces = {}     # quantised: the decode workspace per number of new tokens
         # tokens held per batch row: the device vector the kernels read and its host mirror
         self.length = torch.zeros(batch_size, dtype=torch.int32, device="cuda")
@@ -115,16 +114,6 @@ class KVCache:
         if self.kv_dtype == "fp8":
             per_layer += 2 * self.batch_size * self.n_kv_head * self.n_positions * 4
         return self.n_layer * per_layer
-
-    def scratch(self):
-        """The fp32 (K, V) scratch of a quantised cache, one layer's size and layout, shared by the
-        layers: an extend step dequantises the visible rows into it. Allocated at the first use."""
-        import torch
-        if self._scratch is None:
-            self._scratch = tuple(
-                Tensor(TensorData(torch.empty(self._numel, dtype=torch.float32, device="cuda"), self._shape,
-                                  self._strides), backend=self.backend) for _ in range(2))
-        return self._scratch
 
     def decode_workspace(self, n_new: int):
         """The split-KV workspace of a decode step of n_new tokens on a quantised cache (None when
@@ -278,8 +267,8 @@ class PagedKVCache:
 
     It exposes what the model uses of ``KVCache``. A decode step appends through the table
     (``mt_kv_cache_append_paged``) and reads the pages directly (``mt_flash_attn_decode_paged``);
-    an extend step gathers the visible rows into one contiguous fp32 scratch pair shared by the
-    layers (``mt_kv_cache_gather_paged``) for the extend kernel."""
+    an extend step does the same (``mt_flash_attn_extend_paged``): the pools and the table are all
+    the device memory the cache holds."""
 
     paged = True
     quantised = False
@@ -291,7 +280,7 @@ class PagedKVCache:
             raise ValueError(f"PagedKVCache stores fp32 pages: kv_dtype={kv_dtype!r} is not supported "
                              "(a quantised paged cache is out of scope)")
         if any(getattr(backend, f, None) is None
-               for f in ("kv_cache_append_paged", "flash_attention_decode_paged", "kv_cache_gather_paged")):
+               for f in ("kv_cache_append_paged", "flash_attention_decode_paged", "flash_attention_extend_paged")):
             raise ValueError("PagedKVCache needs a backend with the paged-cache kernels (HipKernelOps)")
         if int(page_size) != page_size or page_size < 16 or page_size & (page_size - 1):
             raise ValueError(f"PagedKVCache: page_size must be a power of two >= 16, got {page_size}")
@@ -326,7 +315,6 @@ class PagedKVCache:
         self.block_table = torch.full((batch_size, W), -1, dtype=torch.int32, device="cuda")
         self._shared = False      # share_prefix was used: a page may have more than one reference
         self._reserved = None     # (lengths, new_lengths) of the last reserve, while the table is as it left it
-        self._scratch = None      # the contiguous fp32 K / V pair of one layer's size for extend steps
         self._workspaces = {}     # the decode workspace per number of new tokens
         self.length = torch.zeros(batch_size, dtype=torch.int32, device="cuda")
         self.length_host = np.zeros(batch_size, dtype=np.int64)
@@ -353,18 +341,6 @@ class PagedKVCache:
 
     def refcount(self, page: int) -> int:
         return self.allocator.refcount(page)
-
-    def scratch(self):
-        """The contiguous fp32 (K, V) pair of one layer, [B, Hkv, W * P, d] in KVCache's layout,
-        shared by the layers: an extend step gathers the visible rows into it. Allocated at the
-        first use."""
-        import torch
-        if self._scratch is None:
-            B, H, N, d = self.batch_size, self.n_kv_head, self.width * self.page_size, self.head_dim
-            self._scratch = tuple(
-                Tensor(TensorData(torch.empty(B * N * H * d, dtype=torch.float32, device="cuda"), (B, H, N, d),
-                                  (N * H * d, d, H * d, 1)), backend=self.backend) for _ in range(2))
-        return self._scratch
 
     def decode_workspace(self, n_new: int):
         """The split-KV workspace of a decode step of n_new tokens (None when the plan has one

@@ -257,7 +257,8 @@ class MultiHeadAttention(Module):
         (a right-padded batch, any seq_len >= 1). All seq_len projected K / V rows are appended
         at the cache's lengths (the padding rows land in the stale tail, which is never read, or
         are dropped past the capacity), then the queries attend the cache
-        (Tensor.flash_attention_extend)."""
+        (Tensor.flash_attention_extend; a paged or a quantised cache is read in place by the extend
+        kernel's own entry points, with the bits a contiguous fp32 copy of the same rows would give)."""
         kvc = lkv.cache
         batch_size, _, seq_len, _ = q.shape
         new_len = _new_token_counts(kv_len, batch_size, seq_len)
@@ -266,21 +267,16 @@ class MultiHeadAttention(Module):
                              f"{int(kvc.length_host.max())} held)")
         visible, q_len = kvc.extend_counts(new_len)
         if kvc.paged:
-            # only the real rows land (count = q_len: there is no stale tail for the padding); no
-            # extend kernel reads pages: the visible rows (the new ones included) are gathered into
-            # the cache's contiguous fp32 scratch, one extra fp32 write and read of them
+            # only the real rows land (count = q_len: there is no stale tail for the padding); the
+            # extend kernel reads the pages through the table
             kvc.reserve(kvc.length_host + new_len)
             q.backend.kv_cache_append_paged(k, v, lkv.k, lkv.v, kvc.block_table, kvc.length, q_len)
-            ks, vs = kvc.scratch()
-            q.backend.kv_cache_gather_paged(lkv.k, lkv.v, kvc.block_table, visible, ks, vs)
-            result = q.flash_attention_extend(ks, vs, visible, q_len)
+            result = q.backend.flash_attention_extend_paged(q, lkv.k, lkv.v, kvc.block_table, visible, q_len, True)
         elif kvc.quantised:
-            # no extend kernel reads a quantised cache: the visible rows (the new ones included) are
-            # dequantised into the cache's fp32 scratch, one extra fp32 write and read of them
+            # the extend kernel widens the quantised rows as it stages them
             q.backend.kv_cache_append_quant(k, v, lkv.k, lkv.v, kvc.length, lkv.k_scale, lkv.v_scale)
-            ks, vs = kvc.scratch()
-            q.backend.kv_cache_dequant(lkv.k, lkv.v, lkv.k_scale, lkv.v_scale, visible, ks, vs)
-            result = q.flash_attention_extend(ks, vs, visible, q_len)
+            result = q.backend.flash_attention_extend_kvq(q, lkv.k, lkv.v, lkv.k_scale, lkv.v_scale, visible,
+                                                          q_len, True)
         else:
             q.backend.kv_cache_append(k, v, lkv.k, lkv.v, kvc.length)
             result = q.flash_attention_extend(lkv.k, lkv.v, visible, q_len)

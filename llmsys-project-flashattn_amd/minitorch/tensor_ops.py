@@ -135,10 +135,12 @@ class TensorBackend:
         # quantised KV cache (optional: KVCache(kv_dtype=...) needs them)
         self.kv_cache_append_quant = getattr(ops, "kv_cache_append_quant", None)
         self.flash_attention_decode_kvq = getattr(ops, "flash_attention_decode_kvq", None)
+        self.flash_attention_extend_kvq = getattr(ops, "flash_attention_extend_kvq", None)
         self.kv_cache_dequant = getattr(ops, "kv_cache_dequant", None)
         # paged KV cache (optional: PagedKVCache needs them)
         self.kv_cache_append_paged = getattr(ops, "kv_cache_append_paged", None)
         self.flash_attention_decode_paged = getattr(ops, "flash_attention_decode_paged", None)
+        self.flash_attention_extend_paged = getattr(ops, "flash_attention_extend_paged", None)
         self.kv_cache_gather_paged = getattr(ops, "kv_cache_gather_paged", None)
         # the next token chosen on the device (optional: a backend without it keeps the host argmax)
         self.select_token = getattr(ops, "select_token", None)

@@ -48,6 +48,22 @@ dtype), 512 new tokens on a cached prefix of n - 512, alternated in one process 
 
 The script exits non-zero unless the extend step is faster than the full forward at every row.
 
+--extend-legs then (--extend-src-legs: only) writes profiles/extend_src_bench.json: per row of
+EXTEND_ROWS the same 512-token causal step on the caches a serving loop holds, fp32 queries and O in the
+paged and quantised legs, alternated in one process and swapping places each round:
+
+  extend         the plain leg above, unchanged (the row's own dtype)
+  paged_direct   one mt_flash_attn_extend_paged step on fp32 pools, P = 16, pages shuffled by one randperm
+  paged_gather   its yardstick, the two launches it replaces: mt_kv_cache_gather_paged into a contiguous
+                 fp32 pair, then mt_flash_attn_extend on it
+  kvq_direct_*   one mt_flash_attn_extend_kvq step on bf16 / e4m3 caches
+  kvq_dequant_*  its yardstick: mt_kv_cache_dequant into an fp32 pair, then mt_flash_attn_extend(MT_F32)
+
+Each leg rotates over enough caches (pools) to exceed twice the Infinity Cache; a direct leg and its
+yardstick read the same sets. The script exits non-zero if a direct leg's median exceeds its two-launch
+yardstick of the same run. --lib PATH loads another build of the library (an A/B against an older one:
+the legs whose entry points it lacks are left out).
+
 --kvq-legs instead writes profiles/decode_kvq_bench.json: per shape of KVQ_SHAPES and Hkv in {H, H/4},
 Nq = 1, fp32 queries and O in every leg, alternated in one process and swapping places each round:
 
@@ -342,6 +358,141 @@ def extend_legs(args, torch, _hip):
               if not r["extend_faster_than_full"]]
     if slower:
         raise SystemExit(f"the extend step is not faster than the full causal forward at {slower}")
+
+
+def bench_extend_src(torch, _hip, B, H, Hkv, n, d, name, rounds, warmup, new=EXTEND_NEW, P=16):
+    """The plain extend leg of bench_extend, and the step on paged and quantised caches against the two
+    launches each direct kernel replaces."""
+    dt = torch.bfloat16 if name == "bf16" else torch.float32
+    es = 2 if name == "bf16" else 4
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rnd32 = lambda *s: torch.randn(*s, generator=g, device="cuda", dtype=torch.float32)  # noqa: E731
+    have = lambda sym: hasattr(_hip.lib(), sym)  # noqa: E731
+
+    def nsets(kv_bytes):  # more than twice the Infinity Cache for every leg (the smallest set here is 17.8 MB)
+        return max(2, -(-2 * ICACHE // kv_bytes) + 1)
+    # the plain leg: bench_extend's, in the row's dtype
+    kv_bytes = 2 * B * Hkv * n * d * es
+    nset = nsets(kv_bytes)
+    caches = [(rnd32(B, n, Hkv, d).to(dt).permute(0, 2, 1, 3), rnd32(B, n, Hkv, d).to(dt).permute(0, 2, 1, 3))
+              for _ in range(nset)]
+    q = rnd32(B, new, H, d).to(dt).permute(0, 2, 1, 3)
+    o = torch.empty((B, new, H, d), dtype=dt, device="cuda").permute(0, 2, 1, 3)
+    # the paged and quantised legs: fp32 queries and O, as DecoderLM runs them
+    q32 = rnd32(B, new, H, d).permute(0, 2, 1, 3)
+    o32 = torch.empty((B, new, H, d), dtype=torch.float32, device="cuda").permute(0, 2, 1, 3)
+    m, l = (torch.empty((B, H, new), dtype=torch.float32, device="cuda") for _ in range(2))
+    qln = torch.full((B,), new, dtype=torch.int32, device="cuda")
+    kvl = torch.full((B,), n, dtype=torch.int32, device="cuda")
+    # one contiguous fp32 pair, KVCache's layout: what the gather and the dequantising copy fill
+    sk, sv = (torch.empty((B, n, Hkv, d), dtype=torch.float32, device="cuda").permute(0, 2, 1, 3) for _ in range(2))
+    scratch_bytes = 2 * B * Hkv * n * d * 4
+
+    W = n // P
+    assert W * P == n
+    pool_bytes = 2 * B * W * P * Hkv * d * 4
+    pset = nsets(pool_bytes)
+    pools = [(rnd32(B * W, P, Hkv, d).permute(0, 2, 1, 3), rnd32(B * W, P, Hkv, d).permute(0, 2, 1, 3))
+             for _ in range(pset)]
+    table = torch.randperm(B * W, generator=g, device="cuda").to(torch.int32).view(B, W)
+
+    def quantised(kv):
+        dq = torch.bfloat16 if kv == "bf16" else torch.uint8
+        nb = 2 * B * Hkv * n * d * (2 if kv == "bf16" else 1) + (2 * B * Hkv * n * 4 if kv == "fp8" else 0)
+        sets = []
+        for _ in range(nsets(nb)):
+            kc, vc = (torch.empty((B, n, Hkv, d), dtype=dq, device="cuda").permute(0, 2, 1, 3) for _ in range(2))
+            ks = vs = None
+            if kv == "fp8":
+                ks, vs = (torch.empty((B, Hkv, n), dtype=torch.float32, device="cuda") for _ in range(2))
+            for lo in range(0, n, 1024):  # the fp32 rows to quantise, a slice at a time
+                kn, vn = (rnd32(B, 1024, Hkv, d).permute(0, 2, 1, 3) for _ in range(2))
+                _hip.kv_cache_append_quant(kn, vn, kc, vc, torch.full((B,), lo, dtype=torch.int32, device="cuda"), ks, vs)
+            sets.append((kc, vc, ks, vs))
+        return nb, sets
+    qsets = {kv: quantised(kv) for kv in ("bf16", "fp8")}
+
+    def extend(i):
+        kc, vc = caches[i % nset]
+        _hip.flash_extend(q, kc, vc, kv_len=kvl, q_len=qln, causal=True, out=o, m=m, l=l)
+
+    def paged_direct(i):
+        kp, vp = pools[i % pset]
+        _hip.flash_extend_paged(q32, kp, vp, table, kv_len=kvl, q_len=qln, causal=True, out=o32, m=m, l=l)
+
+    def paged_gather(i):
+        kp, vp = pools[i % pset]
+        _hip.kv_cache_gather_paged(kp, vp, table, kv_len=kvl, k_out=sk, v_out=sv)
+        _hip.flash_extend(q32, sk, sv, kv_len=kvl, q_len=qln, causal=True, out=o32, m=m, l=l)
+
+    def kvq_direct(kv):
+        sets = qsets[kv][1]
+
+        def fn(i):
+            kc, vc, ks, vs = sets[i % len(sets)]
+            _hip.flash_extend_kvq(q32, kc, vc, ks, vs, kv_len=kvl, q_len=qln, causal=True, out=o32, m=m, l=l)
+        return fn, 2 * len(sets)
+
+    def kvq_dequant(kv):
+        sets = qsets[kv][1]
+
+        def fn(i):
+            kc, vc, ks, vs = sets[i % len(sets)]
+            _hip.kv_cache_dequant(kc, vc, ks, vs, kv_len=kvl, k_out=sk, v_out=sv)
+            _hip.flash_extend(q32, sk, sv, kv_len=kvl, q_len=qln, causal=True, out=o32, m=m, l=l)
+        return fn, 2 * len(sets)
+    legs = {"extend": (extend, 2 * nset), "paged_gather": (paged_gather, 2 * pset)}
+    pairs = {}  # direct leg -> its yardstick
+    if have("mt_flash_attn_extend_paged"):
+        legs["paged_direct"] = (paged_direct, 2 * pset)
+        pairs["paged_direct"] = "paged_gather"
+    for kv in ("bf16", "fp8"):
+        legs[f"kvq_dequant_{kv}"] = kvq_dequant(kv)
+        if have("mt_flash_attn_extend_kvq"):
+            legs[f"kvq_direct_{kv}"] = kvq_direct(kv)
+            pairs[f"kvq_direct_{kv}"] = f"kvq_dequant_{kv}"
+    for fn, inner in legs.values():
+        for _ in range(warmup):
+            _timed(torch, fn, inner)
+    names = list(legs)
+    times = {k: [] for k in legs}
+    for r in range(rounds):  # the legs alternate inside every round and swap places between rounds
+        for k in names[r % len(names):] + names[:r % len(names)]:
+            fn, inner = legs[k]
+            times[k].append(_timed(torch, fn, inner))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    return {
+        "shape": [B, H, n, d], "dtype": name, "kv_heads": Hkv, "new_tokens": new, "cached_prefix": n - new,
+        "page_size": P, "rounds": rounds, "kv_bytes": kv_bytes, "pool_bytes": pool_bytes,
+        "kvq_bytes": {kv: qsets[kv][0] for kv in qsets},
+        "cache_sets_rotated": {"extend": nset, "paged": pset, **{f"kvq_{kv}": len(qsets[kv][1]) for kv in qsets}},
+        # what each yardstick's copy moves beyond its reads of the cache: one fp32 write and one read of all rows
+        "copy_bytes_written_and_read": 2 * scratch_bytes,
+        **{f"{k}_s_median": med[k] for k in legs}, **{f"{k}_s_min": min(times[k]) for k in legs},
+        **{f"{k}_s_max": max(times[k]) for k in legs},
+        **{f"{k}_round_spread": (max(times[k]) - min(times[k])) / med[k] for k in legs},
+        **{f"{a}_over_{b}": med[a] / med[b] for a, b in pairs.items()},
+        "direct_not_slower": {a: bool(med[a] <= med[b]) for a, b in pairs.items()},
+    }
+
+
+def extend_src_legs(args, torch, _hip):
+    library = "this checkout's"
+    if args.lib:
+        library = os.path.join(os.path.basename(os.path.dirname(_hip.LIB_PATH)), os.path.basename(_hip.LIB_PATH))
+    res = {"device": torch.cuda.get_device_name(0), "library": library, "kernels": []}
+    for B, H, Hkv, n, d, name in EXTEND_ROWS:
+        r = bench_extend_src(torch, _hip, B, H, Hkv, n, d, name, args.rounds, args.warmup)
+        print(json.dumps(r), flush=True)
+        res["kernels"].append(r)
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(args.extend_src_out), exist_ok=True)
+    with open(args.extend_src_out, "w") as f:
+        json.dump(res, f, indent=1)
+    slower = [(r["shape"], r["dtype"], r["kv_heads"], k) for r in res["kernels"]
+              for k, ok in r["direct_not_slower"].items() if not ok]
+    if slower:
+        raise SystemExit(f"a direct extend leg is slower than the two launches it replaces at {slower}")
 
 
 KVQ_SHAPES = [(8, 16, 4096, 64), (1, 16, 16384, 128)]
@@ -686,6 +837,11 @@ def main():
     ap.add_argument("--extend-legs", action="store_true",
                     help="run the extend-attention legs instead, into --extend-out")
     ap.add_argument("--extend-out", default=os.path.join(ROOT, "profiles", "extend_bench.json"))
+    ap.add_argument("--extend-src-legs", action="store_true",
+                    help="run only the paged / quantised extend legs, into --extend-src-out")
+    ap.add_argument("--extend-src-out", default=os.path.join(ROOT, "profiles", "extend_src_bench.json"))
+    ap.add_argument("--lib", default=None,
+                    help="another build of libminitorch_hip.so to load (the extend source legs' A/B)")
     ap.add_argument("--kvq-legs", action="store_true",
                     help="run the quantised-KV-cache decode legs instead, into --kvq-out")
     ap.add_argument("--kvq-out", default=os.path.join(ROOT, "profiles", "decode_kvq_bench.json"))
@@ -701,12 +857,20 @@ def main():
         raise SystemExit("decode_bench.py needs an MI355X (no timing is taken on a CPU)")
     import minitorch
     from minitorch import _hip
+    if args.lib:
+        _hip.use_library(os.path.abspath(args.lib), allow_missing=True)
+    if args.extend_src_legs:
+        return extend_src_legs(args, torch, _hip)
     if args.graph_legs:
         return graph_legs(args, torch, minitorch, _hip)
     if args.gqa_legs:
         return gqa_legs(args, torch, _hip)
     if args.extend_legs:
-        return extend_legs(args, torch, _hip)
+        try:
+            extend_legs(args, torch, _hip)
+        finally:
+            extend_src_legs(args, torch, _hip)
+        return
     if args.kvq_legs:
         return kvq_legs(args, torch, _hip)
     if args.paged_legs:
