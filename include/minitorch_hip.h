@@ -388,6 +388,37 @@ int mt_select_token(const float* logits, int64_t B, int64_t V, int64_t row_strid
                     float* next_f32, int32_t* next_i32, int32_t* done, int32_t* history,
                     int64_t history_stride, const int32_t* step_dev, void* stream);
 
+/* ---- rotary position embedding (RoPE) ---------------------------------------
+ * The head rows of x [B, H, T, d] rotated by their positions, in the half-split ("rotate-half")
+ * convention: element j < d/2 of a row pairs with element j + d/2, and at position p
+ *   out[j]       = x[j]       * cos[p][j] - x[j + d/2] * sin[p][j]
+ *   out[j + d/2] = x[j + d/2] * cos[p][j] + x[j]       * sin[p][j]
+ * inverse != 0 uses -sin: the transpose of the rotation, which is its inverse and its backward.
+ * cos / sin: dense fp32 device tables [n_pos, d/2] built by the host (no sincosf runs on the
+ * device: the result is a function of x and the table rows alone, each output two rounded
+ * products and one rounded sum, or tighter where the compiler fuses them).
+ * x / out: (batch, head, token) element strides with unit-stride d; NULL strides mean dense.
+ * x2 / out2 / H2: an optional second tensor [B, H2, T, d] (K beside Q) rotated in the same
+ * launch at the same positions; x2 == NULL skips it (out2, H2 and its strides are ignored).
+ * Token t of batch row b sits at p = min(max(pos0[b], 0) + t, n_pos - 1): pos0 is a device
+ * int32 [B] read when the kernel runs (a KV cache's lengths; a captured launch replays), or NULL
+ * for 0. The clamp is where padding slots past the last position land; no table row outside
+ * [0, n_pos) is read.
+ * out == x with equal strides (in place) is allowed: one thread owns both halves of its pairs
+ * and loads both before it stores. Any other overlap of inputs and outputs is undefined.
+ * Nothing but the d elements of each addressed row is written. Allocates nothing, does not
+ * synchronise, stream-ordered. dtype: MT_F32 only. With d % 8 == 0, 16-B aligned x, out, cos,
+ * sin and strides divisible by 4 the kernel moves 16 B per access, otherwise one pair per
+ * thread; the choice depends on the arguments alone, never on pos0's contents.
+ * Refused with a status before any device call: B, T, H, d or n_pos <= 0; d odd; d > 256;
+ * dtype != MT_F32; x, out, cos or sin NULL; x2 given with out2 NULL or with H2 <= 0; 2^31 or
+ * more pairs in one launch (B (H + H2) T d / 2: the kernels index them in 32 bits). */
+int mt_rope(int dtype, int inverse,
+            const void* x, void* out, int64_t H, const int64_t* x_strides, const int64_t* out_strides,
+            const void* x2, void* out2, int64_t H2, const int64_t* x2_strides, const int64_t* out2_strides,
+            int64_t B, int64_t T, int64_t d, const float* cos, const float* sin, int64_t n_pos,
+            const int* pos0, void* stream);
+
 /* ---- FlashAttention, reference-compatible host pointers (fp32) ------------ */
 /* reference src/flashattention_kernel.cu:259 */
 void launch_flashattention_forward(float* Q, float* K, float* V, float* O, float* l, float* m,

@@ -18,6 +18,7 @@ from .tensor_ops import *  # noqa: F401,F403
 from .modules_basic import *  # noqa: F401,F403
 from .modules_transfomer import *  # noqa: F401,F403
 from .kv_cache import *  # noqa: F401,F403
+from .rotary import *  # noqa: F401,F403
 
 
 def __getattr__(name):

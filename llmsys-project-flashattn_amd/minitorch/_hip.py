@@ -93,6 +93,8 @@ _PROTOS = {
                                         _i64p, _i64p, _i64p, _i64p, _vp, _vp, _vp]),
     "mt_select_token": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _i64, ctypes.c_uint64, _vp, _i64,
                                _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "mt_rope": (_int, [_int, _int, _vp, _vp, _i64, _i64p, _i64p, _vp, _vp, _i64, _i64p, _i64p,
+                       _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "mt_attn_softmax_fw": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64p, _int, _vp]),
     "mt_attn_softmax_bw": (_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "mt_layernorm_fw": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
@@ -901,6 +903,50 @@ def select_token(logits, temperature: float = 0.0, top_k: int = 0, seed: int = 0
         ptr(seed_dev), -1 if eos_id is None else int(eos_id), out.data_ptr(), out_i32.data_ptr(), ptr(done),
         ptr(history), hs, ptr(step_dev), st), "mt_select_token")
     return out, out_i32
+
+
+def rope(x, cos, sin, pos0=None, inverse: bool = False, out=None, x2=None, out2=None,
+         stream: Optional[int] = None):
+    """Rotary position embedding of the head rows of x [B,H,T,d] (mt_rope; fp32, any strides with
+    unit-stride d) by the fp32 device tables cos / sin [n_pos, d/2], in the half-split convention.
+    Token t of batch row b sits at min(max(pos0[b], 0) + t, n_pos - 1); pos0: a device int32 [B]
+    (used as it is, read when the kernel runs), anything else is converted, None is 0.
+    inverse: the transposed rotation (-sin). out: where the result goes (allocated dense when
+    None; `out is x` rotates in place). x2 / out2: an optional second tensor [B,H2,T,d] (K beside
+    Q) rotated in the same launch. Returns out, or (out, out2) with x2."""
+    torch = _torch()
+    _check_dev(x, cos, sin)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"rope takes a 4-D float32 [B,H,T,d] tensor, got {tuple(x.shape)} {x.dtype}")
+    B, H, T, d = x.shape
+    for t in (cos, sin):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] * 2 != d or not t.is_contiguous():
+            raise ValueError(f"rope: cos / sin must be dense float32 [n_pos, {d // 2}] tables, got {tuple(t.shape)}")
+    if cos.shape != sin.shape:
+        raise ValueError("rope: the cos and sin tables differ in shape")
+    if out is None:
+        out = torch.empty((B, H, T, d), dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (B, H, T, d) or out.dtype != torch.float32 or not out.is_cuda:
+        raise ValueError(f"rope: out must be a device float32 {[B, H, T, d]} tensor")
+    H2 = 0
+    if x2 is not None:
+        _check_dev(x2)
+        if x2.dim() != 4 or x2.dtype != torch.float32 or (x2.shape[0], x2.shape[2], x2.shape[3]) != (B, T, d):
+            raise ValueError(f"rope: x2 must be a float32 [{B}, H2, {T}, {d}] tensor, got {tuple(x2.shape)}")
+        H2 = x2.shape[1]
+        if out2 is None:
+            out2 = torch.empty((B, H2, T, d), dtype=torch.float32, device=x.device)
+        if tuple(out2.shape) != tuple(x2.shape) or out2.dtype != torch.float32 or not out2.is_cuda:
+            raise ValueError(f"rope: out2 must be a device float32 {[B, H2, T, d]} tensor")
+    p = _kv_arg(pos0, B, x.device)
+    st = stream_ptr(x.device) if stream is None else stream
+    check(lib().mt_rope(
+        MT_F32, int(bool(inverse)), x.data_ptr(), out.data_ptr(), H, strides3(x), strides3(out),
+        None if x2 is None else x2.data_ptr(), None if x2 is None else out2.data_ptr(), H2,
+        None if x2 is None else strides3(x2), None if x2 is None else strides3(out2),
+        B, T, d, cos.data_ptr(), sin.data_ptr(), cos.shape[0], None if p is None else p.data_ptr(), st),
+        "mt_rope")
+    return out if x2 is None else (out, out2)
 
 
 def scratch_bytes() -> int:

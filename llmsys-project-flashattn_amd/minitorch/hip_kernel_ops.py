@@ -653,3 +653,32 @@ class HipKernelOps(TensorOps):
                 r = torch.as_tensor(np.asarray(rows, dtype=np.int64), device=v.device)
                 v = v[torch.arange(v.shape[0], device=v.device), r]
         return _hip.select_token(v, temperature, top_k, seed, **kw)
+
+    @staticmethod
+    def rope(x: Tensor, cos: Tensor, sin: Tensor, pos0=None, inverse: bool = False, x2: Optional[Tensor] = None,
+             inplace: bool = False):
+        """Rotary position embedding of x [B,H,T,d] by the device tables cos / sin [n_pos, d/2]
+        (mt_rope); token t of row b sits at min(max(pos0[b], 0) + t, n_pos - 1). pos0: None (0), a
+        [B] minitorch Tensor, or a torch int32 device vector (a KVCache's length: read by the kernel,
+        untouched by the host). inverse: the transposed rotation (the backward). x2: a second tensor
+        [B,H2,T,d] rotated in the same launch; the result is then a pair. The outputs are laid out
+        like their inputs' storage (as _flash_fw does); inplace=True writes into the inputs'
+        storage instead and returns tensors over it (no history: inference only)."""
+        import torch
+        tensors = [x] if x2 is None else [x, x2]
+        if not inplace:  # the kernel wants unit-stride head rows (a gradient may come transposed)
+            tensors = [t if t._tensor.strides[-1] == 1 or t.shape[-1] == 1 else t.contiguous() for t in tensors]
+        views = [_torch_view(t) for t in tensors]
+        if inplace:
+            outs, res = views, [_wrap(t._tensor._storage, t.shape, t.backend, t._tensor.strides) for t in tensors]
+        else:
+            outs, res = [], []
+            for t in tensors:
+                lay = _layout_like(t)
+                buf = torch.empty(t.size, dtype=torch.float32, device="cuda")
+                outs.append(torch.as_strided(buf, t.shape, lay))
+                res.append(_wrap(buf, t.shape, t.backend, lay))
+        _hip.rope(views[0], _torch_view(cos), _torch_view(sin),
+                  pos0=None if pos0 is None else HipKernelOps._i32(pos0), inverse=inverse, out=outs[0],
+                  x2=None if x2 is None else views[1], out2=None if x2 is None else outs[1])
+        return res[0] if x2 is None else (res[0], res[1])

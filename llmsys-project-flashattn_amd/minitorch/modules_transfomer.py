@@ -20,6 +20,7 @@ import numpy as np
 from .module import Module
 from .modules_basic import Dropout, Embedding, FusedLayerNorm, LayerNorm1d, Linear
 from .nn import GELU, softmax
+from .rotary import RotaryTable, apply_rope
 from .tensor_functions import tensor, tensor_from_numpy
 
 # Small host-built index tensors the model makes on every forward (the [B] key-padding lengths
@@ -83,10 +84,15 @@ datatype = np.float32
 class MultiHeadAttention(Module):
     def __init__(self, n_embd: int, n_head: int, causal: bool = False, p_dropout: float = 0.1,
                  bias: bool = True, backend=None, use_fused_kernel: bool = False,
-                 use_flash_attention: bool = False, n_kv_head=None):
+                 use_flash_attention: bool = False, n_kv_head=None, rope=None):
         """n_kv_head: grouped-query attention. The n_head query heads share n_kv_head key / value
         heads in groups of n_head // n_kv_head (query head h uses kv head h // group; 1 is
-        multi-query attention). None: n_head, every head its own K and V."""
+        multi-query attention). None: n_head, every head its own K and V.
+        rope: a RotaryTable (rotary position embedding), or None. Q and K are rotated by their
+        tokens' positions right after the projection, so every attention branch and the KV cache
+        see rotated tensors: by the rope kernel when use_fused_kernel is set and the backend has
+        it, by the tensor-op form otherwise (rotary.apply_rope). With a cache the rotation is
+        always the kernel's, one launch for Q and K, in place, at the cache's device lengths."""
         super().__init__()
         if n_kv_head is None:
             n_kv_head = n_head
@@ -105,6 +111,10 @@ class MultiHeadAttention(Module):
         self.dropout = Dropout(p_dropout)
         self.use_fused_kernel = use_fused_kernel
         self.use_flash_attention = use_flash_attention
+        if rope is not None and rope.head_dim != self.attn_hidden_dim:
+            raise ValueError(f"the RotaryTable was built for head_dim = {rope.head_dim}, the heads have "
+                             f"{self.attn_hidden_dim}")
+        self.rope = rope
 
     def create_causal_mask(self, bs, nh, seq_len):
         """Additive -FLT_MAX·triu(1) mask (reference :63-71), [1, 1, T, T] broadcast."""
@@ -187,6 +197,12 @@ class MultiHeadAttention(Module):
         batch_size, seq_len, n_embd = x.shape
         q, k, kT, v = self.project_to_query_key_value(x)
         if cache is None:
+            if self.rope is not None:
+                # training / a full forward: token t sits at position t; differentiable
+                fused = bool(self.use_fused_kernel) and getattr(q.backend, "rope", None) is not None
+                q = apply_rope(q, self.rope, None, fused=fused)
+                k = apply_rope(k, self.rope, None, fused=fused)
+                kT = k.permute(0, 1, 3, 2)
             attn = self.self_attention(q, k if self.use_flash_attention else kT, v, kv_len)
         else:
             attn = self._cached_attention(q, k, v, kv_len, cache)
@@ -213,6 +229,7 @@ class MultiHeadAttention(Module):
         if int(kvc.length_host.max()) + seq_len > kvc.n_positions:
             raise ValueError(f"{seq_len} new tokens do not fit the KV cache ({kvc.n_positions} positions, "
                              f"{int(kvc.length_host.max())} held)")
+        q, k = self._rotate_cached(q, k, None if prefill else kvc.length)
         if kvc.paged:
             return self._paged_attention(q, k, v, kv_len, lkv, prefill)
         if kvc.quantised:
@@ -229,6 +246,19 @@ class MultiHeadAttention(Module):
             result = q.flash_attention_decode(lkv.k, lkv.v, kvc.visible(seq_len))
         result = result.permute(0, 2, 1, 3).contiguous()
         return result.view(batch_size, seq_len, self.n_embd)
+
+    def _rotate_cached(self, q, k, pos0):
+        """Q and K of a cached step rotated in one two-tensor launch, in place in the projections'
+        own buffers (inference: nothing differentiates through a cache). pos0: the cache's device
+        lengths (a decode or extend step: row b's tokens continue at length[b], read by the kernel,
+        so a captured step replays), or None for a prefill. Padding slots that pass the last
+        position take it (mt_rope's clamp); their outputs are discarded."""
+        if self.rope is None:
+            return q, k
+        if getattr(q.backend, "rope", None) is None:
+            raise NotImplementedError("a rotary model with a KV cache needs a backend with the rope kernel "
+                                      "(HipKernelOps)")
+        return q.backend.rope(q, self.rope.cos, self.rope.sin, pos0=pos0, x2=k, inplace=True)
 
     def _paged_attention(self, q, k, v, kv_len, lkv, prefill):
         """A prefill or a decode step on a PagedKVCache: the pages are reserved from the host
@@ -265,6 +295,7 @@ class MultiHeadAttention(Module):
         if (kvc.length_host + new_len > kvc.n_positions).any() or seq_len > kvc.n_positions:
             raise ValueError(f"the new tokens do not fit the KV cache ({kvc.n_positions} positions, "
                              f"{int(kvc.length_host.max())} held)")
+        q, k = self._rotate_cached(q, k, kvc.length)
         visible, q_len = kvc.extend_counts(new_len)
         if kvc.paged:
             # only the real rows land (count = q_len: there is no stale tail for the padding); the
@@ -311,12 +342,13 @@ class TransformerLayer(Module):
 
     def __init__(self, n_embd: int, n_head: int, p_dropout: float = 0.1, ln_eps: float = 1e-8,
                  bias: bool = True, backend=None, use_fused_kernel: bool = False,
-                 use_flash_attention: bool = False, causal: bool = True, n_kv_head=None):
+                 use_flash_attention: bool = False, causal: bool = True, n_kv_head=None, rope=None):
         super().__init__()
         self.attention = MultiHeadAttention(n_embd, n_head, causal=causal, p_dropout=p_dropout,
                                             bias=bias, backend=backend,
                                             use_fused_kernel=use_fused_kernel,
-                                            use_flash_attention=use_flash_attention, n_kv_head=n_kv_head)
+                                            use_flash_attention=use_flash_attention, n_kv_head=n_kv_head,
+                                            rope=rope)
         self.ff = FeedForward(n_embd, 256, p_dropout, bias, backend)
         self.use_fused_kernel = use_fused_kernel
         if use_fused_kernel:
@@ -346,19 +378,30 @@ class DecoderLM(Module):
     def __init__(self, n_vocab: int, n_embd: int, n_head: int, n_positions: int,
                  p_dropout: float = 0.1, ln_eps: float = 1e-5, bias: bool = True, backend=None,
                  use_fused_kernel: bool = False, use_flash_attention: bool = False, n_layer: int = 4,
-                 n_kv_head=None):
+                 n_kv_head=None, pos_encoding: str = "learned", rope_theta: float = 10000.0):
+        """pos_encoding: "learned" adds a learned position_embeddings row to every token's
+        embedding (the reference's model); "rope" has no position parameter: one RotaryTable
+        (n_positions rows, base rope_theta), shared by all layers, rotates every layer's Q and K
+        (MultiHeadAttention(rope=...)) and the token embeddings are fed alone."""
         super().__init__()
+        if pos_encoding not in ("learned", "rope"):
+            raise ValueError(f'pos_encoding must be "learned" or "rope", got {pos_encoding!r}')
         self.backend = backend
         self.n_embd = n_embd
         self.n_vocab = n_vocab
         self.n_layer = n_layer
+        self.pos_encoding = pos_encoding
         self.token_embeddings = Embedding(n_vocab, n_embd, backend)
-        self.position_embeddings = Embedding(n_positions, n_embd, backend)
+        self.rope = None
+        if pos_encoding == "rope":
+            self.rope = RotaryTable(n_positions, n_embd // n_head, rope_theta, backend=backend)
+        else:
+            self.position_embeddings = Embedding(n_positions, n_embd, backend)
         for i in range(n_layer):
             setattr(self, f"t_layer_{i + 1}", TransformerLayer(
                 n_embd, n_head, p_dropout, ln_eps, bias, backend,
                 use_fused_kernel=use_fused_kernel, use_flash_attention=use_flash_attention,
-                n_kv_head=n_kv_head))
+                n_kv_head=n_kv_head, rope=self.rope))
         self.dropout = Dropout(p_dropout)
         self.lm_head = Linear(n_embd, n_vocab, bias, backend)
         self.use_fused_kernel = use_fused_kernel
@@ -382,8 +425,11 @@ class DecoderLM(Module):
         if cache is not None:
             return self._forward_cached(idx, kv_len, cache)
         batch_size, seq_len = idx.shape
-        pos = _positions(seq_len, self.backend)
-        h = self.token_embeddings(idx) + self.position_embeddings(pos).view(1, seq_len, self.n_embd)
+        if self.rope is not None:  # rotary: the positions enter in every layer's attention
+            h = self.token_embeddings(idx)
+        else:
+            pos = _positions(seq_len, self.backend)
+            h = self.token_embeddings(idx) + self.position_embeddings(pos).view(1, seq_len, self.n_embd)
         h = self.dropout(h)
         for i in range(self.n_layer):
             h = getattr(self, f"t_layer_{i + 1}")(h, kv_len)
@@ -420,8 +466,11 @@ class DecoderLM(Module):
         pos = cache.length_host[:, None] + np.arange(seq_len)[None, :]
         if int(pos.max()) >= min(self.n_positions, cache.n_positions):
             raise ValueError(f"position {int(pos.max())} is past n_positions = {self.n_positions}")
-        pos = tensor_from_numpy(np.ascontiguousarray(pos, dtype=datatype), backend=self.backend)
-        h = self.token_embeddings(idx) + self.position_embeddings(pos)
+        if self.rope is not None:
+            h = self.token_embeddings(idx)
+        else:
+            pos = tensor_from_numpy(np.ascontiguousarray(pos, dtype=datatype), backend=self.backend)
+            h = self.token_embeddings(idx) + self.position_embeddings(pos)
         h = self.dropout(h)
         for i in range(self.n_layer):
             h = getattr(self, f"t_layer_{i + 1}")(h, kv_len, cache.layer(i))
@@ -449,8 +498,11 @@ class DecoderLM(Module):
                              f"past n_positions = {limit}")
         # padding slots only can pass the last position: they take it (their outputs are discarded)
         pos = np.minimum(cache.length_host[:, None] + np.arange(seq_len)[None, :], self.n_positions - 1)
-        pos = tensor_from_numpy(np.ascontiguousarray(pos, dtype=datatype), backend=self.backend)
-        h = self.token_embeddings(idx) + self.position_embeddings(pos)
+        if self.rope is not None:
+            h = self.token_embeddings(idx)
+        else:
+            pos = tensor_from_numpy(np.ascontiguousarray(pos, dtype=datatype), backend=self.backend)
+            h = self.token_embeddings(idx) + self.position_embeddings(pos)
         h = self.dropout(h)
         for i in range(self.n_layer):
             h = getattr(self, f"t_layer_{i + 1}")(h, new_len, cache.layer(i))
@@ -685,8 +737,11 @@ class DecoderLM(Module):
         from .tensor_data import TensorData
         cache, B = st.cache, st.cache.batch_size
         cache.clamp_to_last_slot()
-        pos = Tensor(TensorData(cache.length.to(torch.float32), (B, 1)), backend=self.backend)
-        h = self.token_embeddings(st.ids) + self.position_embeddings(pos)
+        if self.rope is not None:  # the layers read cache.length on the device themselves
+            h = self.token_embeddings(st.ids)
+        else:
+            pos = Tensor(TensorData(cache.length.to(torch.float32), (B, 1)), backend=self.backend)
+            h = self.token_embeddings(st.ids) + self.position_embeddings(pos)
         h = self.dropout(h)
         for i in range(self.n_layer):
             h = getattr(self, f"t_layer_{i + 1}")(h, None, cache.layer(i))

@@ -371,3 +371,11 @@ class Tensor:
         if fn is None:
             raise NotImplementedError("this backend has no extend attention kernel")
         return fn(self, Kc, Vc, visible, q_len, causal)
+
+    def rope(self, table, pos0=None) -> "Tensor":
+        """Rotary position embedding of the head rows of self [B,H,T,d] by a RotaryTable: token t
+        of batch row b is rotated to position min(max(pos0[b], 0) + t, n_positions - 1) (pos0: a
+        [B] vector, None for 0). One kernel each way where the backend has it (the Rope
+        Function), the tensor-op form otherwise (rotary.apply_rope); differentiable in self."""
+        from .rotary import apply_rope
+        return apply_rope(self, table, pos0)

@@ -458,6 +458,25 @@ class FlashAttentionCausal(Function):
         return g if kv is None else tuple(g) + (0.0,)
 
 
+class Rope(Function):
+    """Rotary position embedding of x [B,H,T,d] as one backend kernel each way (mt_rope): the
+    forward rotates the head rows by the table rows of their positions, the backward applies the
+    transposed rotation (inverse=1) to the incoming gradient. cos / sin are the constant device
+    tables of a RotaryTable and the optional 4th input a constant [B] tensor of first positions;
+    they travel as FlashAttention's kv_len does and get no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, cos, sin, pos=None):
+        ctx.save_for_backward(cos, sin, pos)
+        return x.f.rope(x, cos, sin, pos0=pos)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        cos, sin, pos = ctx.saved_values
+        g = grad_output.f.rope(grad_output, cos, sin, pos0=pos, inverse=True)
+        return (g, 0.0, 0.0) if pos is None else (g, 0.0, 0.0, 0.0)
+
+
 # ---- constructors --------------------------------------------------------------------
 def _backend_or_raise(backend):
     if backend is None:

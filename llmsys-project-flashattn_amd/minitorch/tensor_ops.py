@@ -144,3 +144,5 @@ class TensorBackend:
         self.kv_cache_gather_paged = getattr(ops, "kv_cache_gather_paged", None)
         # the next token chosen on the device (optional: a backend without it keeps the host argmax)
         self.select_token = getattr(ops, "select_token", None)
+        # rotary position embedding as one kernel (optional: a backend without it runs the tensor-op form)
+        self.rope = getattr(ops, "rope", None)

@@ -87,6 +87,19 @@ and dtype in {fp32, bf16}, Nq = 1, alternated in one process and swapping places
 Each leg rotates over enough caches (pools) of its own to exceed twice the Infinity Cache. No gate: the
 ratios paged / contig are recorded. The memory side is recorded too: nbytes of a one-layer KVCache and of
 PagedKVCaches holding a ragged batch of one row of 4096 tokens and seven of 64.
+
+--rope-legs instead writes profiles/rope_bench.json:
+
+  rope / copy   mt_rope on Q and K (one two-tensor launch, [B,T,H,d] storage, positions from a device
+                vector) of an (8,16,1,64) decode step and an (8,16,512,64) extend step, against a
+                device-to-device copy of the same bytes (the floor of a read-once, write-once kernel);
+                alternated, swapping places each round, over sets that exceed twice the Infinity Cache;
+                each leg eagerly (device events around the launches: at these sizes the host's time to
+                issue a launch) and as one captured graph of the same launches (*_graph: the kernels)
+  generate     generate(graph=True) tokens/s with pos_encoding="rope" against "learned", batch 1 and 8,
+                at the sizes of the graph legs, alternated inside every round
+
+No gate: what is measured is recorded.
 """
 import argparse
 import json
@@ -825,6 +838,112 @@ def graph_legs(args, torch, minitorch, _hip):
         json.dump(res, f, indent=1)
 
 
+ROPE_SHAPES = [(8, 16, 1, 64, "decode step"), (8, 16, 512, 64, "extend step")]
+
+
+def bench_rope(torch, minitorch, _hip, B, H, T, d, what, rounds, warmup):
+    """mt_rope on Q and K [B,H,T,d] (the model's [B,T,H,d] projection storage, one two-tensor
+    launch, positions from a device vector) against a device-to-device copy of the same bytes,
+    the floor of a kernel that reads every byte once and writes it once. Both legs rotate over the
+    same source / destination sets, enough of them to exceed twice the Infinity Cache."""
+    n_pos = 4096
+    tab = minitorch.RotaryTable(n_pos, d)
+    cos, sin = torch.from_numpy(tab.cos_host).cuda(), torch.from_numpy(tab.sin_host).cuda()
+    nbytes = 2 * B * H * T * d * 4  # Q and K, read once and written once each
+    sets = max(2, min(64, -(-2 * ICACHE // (2 * nbytes))))
+    g = torch.Generator(device="cuda").manual_seed(0)
+    src = [torch.randn(2, B, T, H, d, generator=g, device="cuda") for _ in range(sets)]
+    dst = [torch.empty_like(s) for s in src]
+    pos0 = torch.randint(0, n_pos - T, (B,), generator=g, device="cuda", dtype=torch.int32)
+    view = lambda t: t.permute(0, 2, 1, 3)  # noqa: E731
+    inner = 64 if T == 1 else 16
+
+    def rope(i):
+        s, o = src[i % sets], dst[i % sets]
+        _hip.rope(view(s[0]), cos, sin, pos0=pos0, out=view(o[0]), x2=view(s[1]), out2=view(o[1]))
+
+    def copy(i):
+        dst[i % sets].copy_(src[i % sets])
+    legs = {"rope": rope, "copy": copy}
+    for fn in legs.values():
+        for _ in range(warmup):
+            _timed(torch, fn, inner)
+    # the same `inner` launches as one captured graph each: an eager leg cannot go below the host's
+    # time to issue a launch, which exceeds these kernels' run time; a replay issues nothing
+    graphs = {}
+    for k, fn in list(legs.items()):
+        graphs[k] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[k]):
+            for i in range(inner):
+                fn(i)
+        legs[k + "_graph"] = lambda i, g=graphs[k]: g.replay()
+        for _ in range(warmup):
+            _timed(torch, legs[k + "_graph"], 4)
+    times = {k: [] for k in legs}
+    for r in range(rounds):
+        for k in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            if k.endswith("_graph"):  # one replay is `inner` launches
+                times[k].append(_timed(torch, legs[k], 4) / inner)
+            else:
+                times[k].append(_timed(torch, legs[k], inner))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    return {"what": what, "B": B, "H": H, "Hkv": H, "T": T, "d": d, "rounds": rounds, "launches_per_timing": inner,
+            "sets": sets, "bytes_read_plus_written": 2 * nbytes,
+            **{f"{k}_s_median": v for k, v in med.items()}, **{f"{k}_s_min": min(v) for k, v in times.items()},
+            "rope_bytes_per_s": 2 * nbytes / med["rope"], "copy_bytes_per_s": 2 * nbytes / med["copy"],
+            "rope_over_copy_time": med["rope"] / med["copy"],
+            "rope_graph_bytes_per_s": 2 * nbytes / med["rope_graph"],
+            "copy_graph_bytes_per_s": 2 * nbytes / med["copy_graph"],
+            "rope_over_copy_time_graph": med["rope_graph"] / med["copy_graph"]}
+
+
+def bench_generate_rope(minitorch, n_positions, prompt_len, new_tokens, batch, rounds):
+    """generate(graph=True) tokens/s of the rotary model against the learned-position model, the
+    sizes of the graph legs; the legs alternate inside every round."""
+    backend = minitorch.TensorBackend(minitorch.HipKernelOps)
+    rng = np.random.default_rng(0)
+    prompts = [[int(t) for t in rng.integers(0, 10000, prompt_len)] for _ in range(batch)]
+    legs, agree = {}, {}
+    for enc in ("learned", "rope"):
+        np.random.seed(0)
+        lm = minitorch.DecoderLM(n_vocab=10000, n_embd=256, n_head=8, n_positions=n_positions, p_dropout=0.0,
+                                 backend=backend, use_fused_kernel=True, use_flash_attention=True, pos_encoding=enc)
+        legs[f"{enc}_graph_one"] = lambda lm=lm: lm.generate(prompts[:1], new_tokens, graph=True)
+        legs[f"{enc}_graph_batch"] = lambda lm=lm: lm.generate(prompts, new_tokens, graph=True)
+        # warm-up (captures the graphs); the graph leg must give the eager cached leg's ids
+        agree[enc] = (legs[f"{enc}_graph_batch"]() == lm.generate(prompts, new_tokens, use_cache=True)
+                      and legs[f"{enc}_graph_one"]() == lm.generate(prompts[:1], new_tokens, use_cache=True))
+    rate = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            toks = fn()  # ends in a device-to-host copy: synchronised
+            rate[k].append(sum(len(t) for t in toks) / (time.perf_counter() - t0))
+    med = {k: statistics.median(v) for k, v in rate.items()}
+    return {"n_positions": n_positions, "prompt_len": prompt_len, "new_tokens": new_tokens, "batch": batch,
+            "rounds": rounds, "graph_equals_eager": agree,
+            **{f"{k}_tokens_per_s_median": v for k, v in med.items()},
+            **{f"{k}_tokens_per_s_best": max(v) for k, v in rate.items()},
+            "rope_over_learned_one": med["rope_graph_one"] / med["learned_graph_one"],
+            "rope_over_learned_batch": med["rope_graph_batch"] / med["learned_graph_batch"]}
+
+
+def rope_legs(args, torch, minitorch, _hip):
+    res = {"device": torch.cuda.get_device_name(0), "kernels": [], "generate": []}
+    for B, H, T, d, what in ROPE_SHAPES:
+        r = bench_rope(torch, minitorch, _hip, B, H, T, d, what, args.rounds, args.warmup)
+        print(json.dumps(r), flush=True)
+        res["kernels"].append(r)
+        torch.cuda.empty_cache()
+    for npos, plen, new, batch, rounds in ((40, 8, 32, 8, 5), (1024, 768, 128, 8, 3)):
+        r = bench_generate_rope(minitorch, npos, plen, new, batch, rounds)
+        print(json.dumps(r), flush=True)
+        res["generate"].append(r)
+    os.makedirs(os.path.dirname(args.rope_out), exist_ok=True)
+    with open(args.rope_out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "decode_bench.json"))
@@ -848,6 +967,9 @@ def main():
     ap.add_argument("--paged-legs", action="store_true",
                     help="run the paged-KV-cache decode legs instead, into --paged-out")
     ap.add_argument("--paged-out", default=os.path.join(ROOT, "profiles", "decode_paged_bench.json"))
+    ap.add_argument("--rope-legs", action="store_true",
+                    help="run the rotary-embedding legs instead, into --rope-out")
+    ap.add_argument("--rope-out", default=os.path.join(ROOT, "profiles", "rope_bench.json"))
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--skip-generate", action="store_true")
@@ -875,6 +997,8 @@ def main():
         return kvq_legs(args, torch, _hip)
     if args.paged_legs:
         return paged_legs(args, torch, minitorch, _hip)
+    if args.rope_legs:
+        return rope_legs(args, torch, minitorch, _hip)
     res = {"device": torch.cuda.get_device_name(0), "kernels": [], "generate": []}
     for B, H, L, d, name in SHAPES:
         r = bench_shape(torch, _hip, B, H, L, d, name, args.rounds, args.warmup)
