@@ -388,6 +388,58 @@ int mt_select_token(const float* logits, int64_t B, int64_t V, int64_t row_strid
                     float* next_f32, int32_t* next_i32, int32_t* done, int32_t* history,
                     int64_t history_stride, const int32_t* step_dev, void* stream);
 
+/* ---- speculative decoding: prompt-lookup drafts, verified on the device ------
+ * Both entries are stream-ordered, allocate nothing, do not synchronise, write with plain stores
+ * and are capturable in a hipGraph; their launches depend on the sizes alone.
+ *
+ * mt_spec_draft: tokens is int32 [B, S] (rows token_stride >= S apart, read only): row b holds
+ * its prompt followed by everything emitted so far, held[b] (device int32) tokens in all. Per
+ * row, with L = clamp(held[b], 1, S):
+ *   feed[b, 0] = tokens[b, L - 1] (the token the next step feeds anyway);
+ *   for g = min(max_ngram, L - 1) down to 1: the largest s in [0, L - g - 1] with
+ *     tokens[b, s .. s + g) == tokens[b, L - g .. L); the first g that has a match wins;
+ *   the k drafts feed[b, 1 + i] = ext[s + g + i], ext being tokens[b, :L] with every draft
+ *     appended as it is made (a match near the end continues periodically into itself), and
+ *     n_draft[b] = k; with no match at any g, n_draft[b] = 0 and the k slots hold feed[b, 0].
+ * feed_f32 / feed_i32: dense [B, k + 1], the ids as floats (what mt_embedding_fw reads) and / or
+ * as int32 (either may be NULL, not both). One 256-thread workgroup per row.
+ * Refused with a status before any device call: k outside 1..7, max_ngram outside 1..8, B or
+ * S <= 0, S < k + 2, token_stride < S, NULL tokens / held / n_draft, both outputs NULL.
+ *
+ * mt_spec_accept: logits is fp32 [B, k + 1, V] (batch rows batch_stride, rows row_stride >= V
+ * elements apart, unit-stride columns, V <= 32768), row i of batch row b being the model's
+ * output after feed[b, 0 .. i]. A batch row with done[b] != 0 on entry changes nothing. Else:
+ *   1. c_i, i = 0..k, is the id mt_select_token defines for the row logits[b, i] with seed
+ *      (seed_dev ? *seed_dev : seed) + count[b] + i and the uniform at index b: the token the
+ *      non-speculative path chooses as the row's token number count[b] + i (greedy and sampling
+ *      rules, NaN and tie rules and the fixed-order sums are mt_select_token's, one kernel).
+ *   2. a = the number of leading i < n_draft[b] with feed[b, 1 + i] == c_i (a padding slot past
+ *      n_draft never counts).
+ *   3. e = min(a + 1, limit[b] - count[b]). c_0 .. c_{e-1} are written to
+ *      history[b, count[b] + j] and tokens[b, held[b] + j] (a slot outside the row is dropped),
+ *      stopping after the first of them that equals eos_id (eos_id < 0: no eos), which is still
+ *      written and sets done[b]. With e' ids written: count[b], held[b] and cache_len[b] grow
+ *      by e' (the fed tokens 0 .. e'-1 are then exactly what the KV cache holds: cache_len ==
+ *      held - 1 is kept); done[b] |= count[b] == limit[b]; drafted[b] += n_draft[b];
+ *      accepted[b] += min(a, e' - 1); steps[b] += 1.
+ * scratch: device int32 [B, k + 1], the caller's, holds c between the two launches (one
+ * workgroup per logits row, then one thread per batch row). cache_len, drafted, accepted and
+ * steps may be NULL. The rejected drafts' K / V rows stay in the cache past cache_len, where
+ * nothing reads them and the next step overwrites them.
+ * Refused with a status before any device call: k outside 1..7, B, V or S <= 0, V > 32768,
+ * S < k + 2, row_stride < V, batch_stride < k row_stride + V, token_stride < S, history_stride
+ * <= 0, a negative or NaN temperature, a NULL required pointer. */
+int mt_spec_draft(const int32_t* tokens, int64_t B, int64_t S, int64_t token_stride, const int32_t* held,
+                  int64_t k, int64_t max_ngram, float* feed_f32, int32_t* feed_i32, int32_t* n_draft,
+                  void* stream);
+int mt_spec_accept(const float* logits, int64_t B, int64_t k, int64_t V, int64_t batch_stride,
+                   int64_t row_stride, const int32_t* feed_i32, const int32_t* n_draft, float temperature,
+                   int64_t top_k, uint64_t seed, const uint64_t* seed_dev, int64_t eos_id,
+                   const int32_t* limit, int32_t* count, int32_t* held, int32_t* cache_len, int32_t* done,
+                   int32_t* drafted, int32_t* accepted, int32_t* steps, int32_t* tokens, int64_t S,
+                   int64_t token_stride, int32_t* history, int64_t history_stride, int32_t* scratch,
+                   void* stream);
+
 /* ---- rotary position embedding (RoPE) ---------------------------------------
  * The head rows of x [B, H, T, d] rotated by their positions, in the half-split ("rotate-half")
  * convention: element j < d/2 of a row pairs with element j + d/2, and at position p

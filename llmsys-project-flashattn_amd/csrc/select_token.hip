@@ -21,33 +21,18 @@
 //      last kept index with e_i > 0 when rounding leaves none.
 // Every sum has a fixed association, so the id is a function of the row's bits, T, top_k, the
 // seed and b alone. Stores are plain vector stores; the only atomics are on the LDS histogram.
+// mt_spec_accept (spec_decode.hip) launches the same kernel over k + 1 logits rows per batch row
+// (select_token.h: SelectArgs.rows, count, skip, scratch): row i of batch row b draws with
+// seed + count[b] + i and b's uniform, and its id goes to the caller's scratch only.
 #include "../../include/minitorch_hip.h"
 #include "fa_common.h"
 #include "rng.h"
+#include "select_token.h"
 #include <math.h>
 
 namespace mt {
 int set_error(const char* fmt, ...);           // capi_flash.hip
 int check_hip(hipError_t e, const char* where);
-
-constexpr int kSelThreads = 256;
-constexpr int kSelMaxV = 32768;  // the row in LDS: 128 KiB of the CU's 160
-
-struct SelectArgs {
-  const float* logits;
-  int64_t row_stride;
-  int V, top_k;
-  float temperature;
-  uint64_t seed;
-  const uint64_t* seed_dev;
-  int64_t eos_id;
-  float* next_f32;
-  int32_t* next_i32;
-  int32_t* done;
-  int32_t* history;
-  int64_t history_stride;
-  const int32_t* step_dev;
-};
 
 // fp32 -> u32 with the floats' order (-0 as +0, as the comparison has it); a NaN above +inf
 __device__ __forceinline__ uint32_t order_key(float x) {
@@ -61,7 +46,11 @@ __device__ __forceinline__ float wave_sum(float v) {  // the same tree on every 
   return v;
 }
 
-__device__ __forceinline__ void write_id(const SelectArgs& a, int b, int id) {
+__device__ __forceinline__ void write_id(const SelectArgs& a, int b, int i, int id) {
+  if (a.scratch) {
+    a.scratch[(int64_t)b * a.rows + i] = id;
+    return;
+  }
   if (a.next_f32) a.next_f32[b] = (float)id;
   if (a.next_i32) a.next_i32[b] = id;
   if (a.done && a.eos_id >= 0 && (int64_t)id == a.eos_id) a.done[b] |= 1;
@@ -81,9 +70,11 @@ __global__ __launch_bounds__(kSelThreads) void select_token_kernel(const SelectA
   __shared__ unsigned sel[2];
   __shared__ int cut_s;
 
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x / a.rows, ri = blockIdx.x - b * a.rows;  // the batch row, the logits row in it
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int V = a.V;
-  const float* rp = a.logits + (int64_t)b * a.row_stride;
+  if (a.skip && a.skip[b]) return;  // workgroup-uniform
+  const float* rp = a.logits + (int64_t)b * a.batch_stride + (int64_t)ri * a.row_stride;
   const bool sampling = a.temperature > 0.f;
 
   // ---- 0: load the row, greedy id --------------------------------------------------------
@@ -120,7 +111,7 @@ __global__ __launch_bounds__(kSelThreads) void select_token_kernel(const SelectA
   const unsigned gkey = (unsigned)(best >> 32);
   // greedy; also a sampling row whose maximum is a NaN or an infinity
   if (!sampling || gkey >= 0xFF800000u || gkey <= 0x007FFFFFu) {
-    if (tid == 0) write_id(a, b, gid);
+    if (tid == 0) write_id(a, b, ri, gid);
     return;
   }
   // The maximum, rebuilt from its key in registers (order_key inverted; -0 comes back as +0).
@@ -243,7 +234,8 @@ __global__ __launch_bounds__(kSelThreads) void select_token_kernel(const SelectA
     if (w == wave) run = total;
     total += sum_w[w];
   }
-  const float target = uniform24(a.seed_dev ? *a.seed_dev : a.seed, b) * total;
+  const uint64_t seed = (a.seed_dev ? *a.seed_dev : a.seed) + (a.count ? (uint64_t)((int64_t)a.count[b] + ri) : 0ull);
+  const float target = uniform24(seed, b) * total;
 
   // ---- 3: the first entry whose running sum exceeds u * total ------------------------------
   int found = 0x7FFFFFFF;
@@ -276,12 +268,12 @@ __global__ __launch_bounds__(kSelThreads) void select_token_kernel(const SelectA
   if (tid == 0) {
     int id = min(min(cand_w[0], cand_w[1]), min(cand_w[2], cand_w[3]));
     if (id == 0x7FFFFFFF) id = max(max(last_w[0], last_w[1]), max(last_w[2], last_w[3]));
-    write_id(a, b, id);
+    write_id(a, b, ri, id);
   }
 }
 
-static hipError_t launch_select(const SelectArgs& a, int64_t B, hipStream_t st) {
-  const dim3 grid((unsigned)B), block(kSelThreads);
+hipError_t launch_select(const SelectArgs& a, int64_t B, hipStream_t st) {
+  const dim3 grid((unsigned)(B * a.rows)), block(kSelThreads);
   if (a.V <= 4096) select_token_kernel<4096><<<grid, block, 0, st>>>(a);
   else if (a.V <= 16384) select_token_kernel<16384><<<grid, block, 0, st>>>(a);
   else select_token_kernel<kSelMaxV><<<grid, block, 0, st>>>(a);
@@ -315,5 +307,6 @@ extern "C" int mt_select_token(const float* logits, int64_t B, int64_t V, int64_
   a.temperature = temperature; a.seed = seed; a.seed_dev = seed_dev; a.eos_id = eos_id;
   a.next_f32 = next_f32; a.next_i32 = next_i32; a.done = done;
   a.history = history; a.history_stride = history_stride; a.step_dev = step_dev;
+  a.rows = 1; a.batch_stride = row_stride; a.count = nullptr; a.skip = nullptr; a.scratch = nullptr;
   return check_hip(launch_select(a, B, (hipStream_t)stream), "mt_select_token");
 }

@@ -93,6 +93,10 @@ _PROTOS = {
                                         _i64p, _i64p, _i64p, _i64p, _vp, _vp, _vp]),
     "mt_select_token": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _i64, ctypes.c_uint64, _vp, _i64,
                                _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "mt_spec_draft": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "mt_spec_accept": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, ctypes.c_float, _i64, ctypes.c_uint64,
+                              _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp,
+                              _vp]),
     "mt_rope": (_int, [_int, _int, _vp, _vp, _i64, _i64p, _i64p, _vp, _vp, _i64, _i64p, _i64p,
                        _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "mt_attn_softmax_fw": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64p, _int, _vp]),
@@ -903,6 +907,92 @@ def select_token(logits, temperature: float = 0.0, top_k: int = 0, seed: int = 0
         ptr(seed_dev), -1 if eos_id is None else int(eos_id), out.data_ptr(), out_i32.data_ptr(), ptr(done),
         ptr(history), hs, ptr(step_dev), st), "mt_select_token")
     return out, out_i32
+
+
+def _spec_vec(who, name, t, n, dtype=None, optional=False):
+    torch = _torch()
+    dtype = torch.int32 if dtype is None else dtype
+    if t is None and optional:
+        return None
+    if t is None or not t.is_cuda or t.dtype != dtype or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous device {dtype} tensor of {n} element(s)")
+    return t.data_ptr()
+
+
+def _spec_rows(who, name, t, B):
+    """(S, row stride) of an int32 device [B, S] tensor with unit-stride rows."""
+    torch = _torch()
+    if (t is None or not t.is_cuda or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != B
+            or (t.shape[1] > 1 and t.stride(1) != 1)):
+        raise ValueError(f"{who}: {name} must be a device int32 [{B}, S] tensor with unit-stride rows")
+    return t.shape[1], (t.stride(0) if B > 1 else max(t.shape[1], t.stride(0)))
+
+
+def spec_draft(tokens, held, k: int, max_ngram: int = 3, feed_f32=None, feed_i32=None, n_draft=None,
+               stream: Optional[int] = None):
+    """Prompt-lookup drafts (mt_spec_draft): tokens int32 [B, S] (row b: the prompt and everything
+    emitted, held[b] tokens; read only), held int32 [B]. Returns (feed_f32, feed_i32, n_draft):
+    the fp32 and int32 [B, k + 1] fed tokens (the last held token, then k drafts) and the int32
+    [B] draft counts, allocated when not given. The rule is the header's."""
+    torch = _torch()
+    who = "spec_draft"
+    if tokens is None or tokens.dim() != 2:
+        raise ValueError(f"{who}: tokens must be a device int32 [B, S] tensor")
+    B = tokens.shape[0]
+    S, ts = _spec_rows(who, "tokens", tokens, B)
+    n = B * (int(k) + 1)
+    if feed_f32 is None:
+        feed_f32 = torch.empty((B, int(k) + 1), dtype=torch.float32, device=tokens.device)
+    if feed_i32 is None:
+        feed_i32 = torch.empty((B, int(k) + 1), dtype=torch.int32, device=tokens.device)
+    if n_draft is None:
+        n_draft = torch.empty(B, dtype=torch.int32, device=tokens.device)
+    st = stream_ptr(tokens.device) if stream is None else stream
+    check(lib().mt_spec_draft(
+        tokens.data_ptr(), B, S, ts, _spec_vec(who, "held", held, B), int(k), int(max_ngram),
+        _spec_vec(who, "feed_f32", feed_f32, n, torch.float32), _spec_vec(who, "feed_i32", feed_i32, n),
+        _spec_vec(who, "n_draft", n_draft, B), st), "mt_spec_draft")
+    return feed_f32, feed_i32, n_draft
+
+
+def spec_accept(logits, feed_i32, n_draft, limit, count, held, done, tokens, history, scratch=None,
+                cache_len=None, drafted=None, accepted=None, steps=None, temperature: float = 0.0, top_k: int = 0,
+                seed: int = 0, seed_dev=None, eos_id=None, stream: Optional[int] = None):
+    """Verify the drafts of one speculative step and do its bookkeeping (mt_spec_accept): logits a
+    3-D fp32 device view [B, k + 1, V] with unit-stride columns; feed_i32 / n_draft as spec_draft
+    wrote them; limit, count, held, done (and the optional cache_len, drafted, accepted, steps)
+    int32 [B]; tokens, history int32 [B, S] / [B, S']; scratch int32 [B, k + 1] (allocated when
+    None; pass one inside a captured step). seed / seed_dev: the call's base seed (token number
+    count[b] + i draws with base + count[b] + i). Everything is updated in place; returns scratch,
+    which then holds the k + 1 chosen ids of every row that was not done."""
+    torch = _torch()
+    who = "spec_accept"
+    _check_dev(logits)
+    if logits.dim() != 3 or logits.dtype != torch.float32:
+        raise ValueError(f"{who} takes a 3-D float32 [B, k + 1, V] view, got {tuple(logits.shape)} {logits.dtype}")
+    B, n, V = logits.shape
+    if V > 1 and logits.stride(2) != 1:
+        raise ValueError(f"{who}: the vocabulary dimension must be unit-stride")
+    k = n - 1
+    row_stride = logits.stride(1) if n > 1 else max(V, logits.stride(1))
+    batch_stride = logits.stride(0) if B > 1 else max(k * row_stride + V, logits.stride(0))
+    if scratch is None:
+        scratch = torch.empty((B, n), dtype=torch.int32, device=logits.device)
+    S, ts = _spec_rows(who, "tokens", tokens, B)
+    hs, hstride = _spec_rows(who, "history", history, B)
+    if B > 1 and hstride != hs:
+        raise ValueError(f"{who}: history rows must be contiguous")
+    v = lambda name, t, m=B, **kw: _spec_vec(who, name, t, m, **kw)  # noqa: E731
+    st = stream_ptr(logits.device) if stream is None else stream
+    check(lib().mt_spec_accept(
+        logits.data_ptr(), B, k, V, batch_stride, row_stride, v("feed_i32", feed_i32, B * n), v("n_draft", n_draft),
+        float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF,
+        v("seed_dev", seed_dev, 1, dtype=torch.int64, optional=True), -1 if eos_id is None else int(eos_id),
+        v("limit", limit), v("count", count), v("held", held), v("cache_len", cache_len, optional=True),
+        v("done", done), v("drafted", drafted, optional=True), v("accepted", accepted, optional=True),
+        v("steps", steps, optional=True), tokens.data_ptr(), S, ts, history.data_ptr(), hs,
+        v("scratch", scratch, B * n), st), "mt_spec_accept")
+    return scratch
 
 
 def rope(x, cos, sin, pos0=None, inverse: bool = False, out=None, x2=None, out2=None,

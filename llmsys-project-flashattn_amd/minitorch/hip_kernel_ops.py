@@ -655,6 +655,24 @@ class HipKernelOps(TensorOps):
         return _hip.select_token(v, temperature, top_k, seed, **kw)
 
     @staticmethod
+    def spec_draft(tokens, held, k: int, max_ngram: int = 3, **kw):
+        """Prompt-lookup drafts for a speculative step (mt_spec_draft): tokens int32 [B, S] and held
+        int32 [B] torch device tensors; returns (feed_f32, feed_i32 [B, k + 1], n_draft [B]). The
+        keywords (feed_f32, feed_i32, n_draft: outputs to write into) are _hip.spec_draft's."""
+        return _hip.spec_draft(tokens, held, k, max_ngram, **kw)
+
+    @staticmethod
+    def spec_accept(logits, feed_i32, n_draft, limit, count, held, done, tokens, history, **kw):
+        """Verify a speculative step's drafts against logits [B, k + 1, V] (a minitorch Tensor, or
+        [B (k + 1), V] with k + 1 taken from feed_i32, or a torch view) and advance the row state in
+        place (mt_spec_accept). The keywords (scratch, cache_len, drafted, accepted, steps,
+        temperature, top_k, seed, seed_dev, eos_id) are _hip.spec_accept's."""
+        v = _torch_view(logits) if isinstance(logits, Tensor) else logits
+        if v.dim() == 2:
+            v = v.view(feed_i32.shape[0], -1, v.shape[1])
+        return _hip.spec_accept(v, feed_i32, n_draft, limit, count, held, done, tokens, history, **kw)
+
+    @staticmethod
     def rope(x: Tensor, cos: Tensor, sin: Tensor, pos0=None, inverse: bool = False, x2: Optional[Tensor] = None,
              inplace: bool = False):
         """Rotary position embedding of x [B,H,T,d] by the device tables cos / sin [n_pos, d/2]

@@ -411,6 +411,7 @@ class DecoderLM(Module):
         self.n_kv_head = n_head if n_kv_head is None else n_kv_head
         self.ln = FusedLayerNorm(n_embd, backend) if use_fused_kernel else LayerNorm1d(n_embd, ln_eps, backend)
         self.graph_captures = 0  # hipGraph captures of the decode step (generate(graph=True))
+        self.spec_stats = None   # the last generate(speculate=...) call's counters
 
     def forward(self, idx, kv_len=None, cache=None):
         """kv_len: optional valid-token count per batch row of a right-padded batch (keys past
@@ -540,7 +541,7 @@ class DecoderLM(Module):
 
     def generate(self, prompts, max_new_tokens: int, eos_id=None, use_cache: bool = True,
                  temperature: float = 0.0, top_k: int = 0, seed=None, graph: bool = False, sync_every: int = 8,
-                 prefill_chunk=None, kv_dtype=None, page_size=None):
+                 prefill_chunk=None, kv_dtype=None, page_size=None, speculate=None, ngram: int = 3):
         """Decoding of a list of token-id lists, as the reference's generate
         (project/run_machine_translation.py:271-328); returns the new ids per prompt (without
         the eos that stopped a row). A row also stops once it holds more than n_positions tokens.
@@ -586,7 +587,23 @@ class DecoderLM(Module):
         sum_b ceil(min(len_b + max_new_tokens, n_positions) / P), instead of B * n_positions rows.
         Every row is reserved to that length before the first step, so the block table is fixed
         while a graph is captured and replays (graph=True budgets at least 3 tokens per row, the
-        steps a capture runs). The ids are those of the contiguous cache."""
+        steps a capture runs). The ids are those of the contiguous cache.
+
+        speculate=k (1..7; needs use_cache=True and the spec_draft / spec_accept kernels; None or 0:
+        off, nothing changes): speculative decoding with prompt-lookup drafts. Every step drafts up
+        to k tokens per row as the continuation of the latest earlier occurrence of the row's last
+        n-gram (the longest n <= ngram, 1..8, that occurs; mt_spec_draft), feeds the last token and
+        the drafts through one (k + 1)-token decode step, chooses on the device the token the
+        non-speculative path would choose at each of the k + 1 places (token number t of a row
+        draws with seed + t and the row's uniform, as above) and keeps the drafts that equal them
+        plus one more token (mt_spec_accept), so a step emits 1 to k + 1 tokens per row and the
+        ids are those of the same call without speculate, greedy or sampled. The rejected drafts'
+        K / V rows stay past the cache's length and are overwritten by the next step. Nothing goes
+        through the host inside a step: graph=True replays it from one captured graph (kept per
+        batch size, cache kind, k and ngram), graph=False calls it directly; the `done` flags are
+        read every sync_every steps. Afterwards spec_stats holds dict(steps, tokens, drafted,
+        accepted): the steps run while any row was live, the ids chosen (a stopping eos and every
+        row's first token, chosen by the prefill, included), the drafts made and those accepted."""
         prompts = [[int(t) for t in p] for p in prompts]
         if not prompts or any(len(p) == 0 for p in prompts):
             raise ValueError("generate needs at least one prompt and no empty prompt")
@@ -620,8 +637,20 @@ class DecoderLM(Module):
             if int(prefill_chunk) != prefill_chunk or prefill_chunk < 1:
                 raise ValueError(f"prefill_chunk must be a whole number >= 1, got {prefill_chunk}")
             prefill_chunk = int(prefill_chunk)
+        if speculate:  # None / 0: off
+            if int(speculate) != speculate or not 1 <= speculate <= 7:
+                raise ValueError(f"speculate must be None, 0 or a whole number in 1..7 (a decode step takes "
+                                 f"k + 1 <= 8 tokens), got {speculate}")
+            if int(ngram) != ngram or not 1 <= ngram <= 8:
+                raise ValueError(f"ngram must be a whole number in 1..8, got {ngram}")
+            if not use_cache:
+                raise ValueError("generate(speculate=...) verifies drafts against a KV cache: it needs use_cache=True")
+            if any(getattr(self.backend, f, None) is None for f in ("spec_draft", "spec_accept", "select_token")):
+                raise ValueError("generate(speculate=...) drafts and verifies tokens on the device: it needs a "
+                                 "backend with the spec_draft / spec_accept and select_token kernels (HipKernelOps)")
+            speculate, ngram = int(speculate), int(ngram)
         sampler = None
-        if temperature > 0.0 or graph:
+        if temperature > 0.0 or graph or speculate:
             if getattr(self.backend, "select_token", None) is None:
                 raise ValueError("sampling and graph=True choose tokens on the device: they need a backend "
                                  "with the select_token kernel (HipKernelOps)")
@@ -633,6 +662,9 @@ class DecoderLM(Module):
         was_training = self.training
         self.eval()
         try:
+            if speculate:
+                return self._generate_spec(prompts, max_new_tokens, eos_id, sampler, max(1, int(sync_every)),
+                                           prefill_chunk, kv_dtype, page_size, speculate, ngram, bool(graph))
             if graph:
                 return self._generate_graph(prompts, max_new_tokens, eos_id, sampler, max(1, int(sync_every)),
                                             prefill_chunk, kv_dtype, page_size)
@@ -844,6 +876,136 @@ class DecoderLM(Module):
                     break
         return new
 
+    # ---- speculative decoding: prompt-lookup drafts verified in one (k + 1)-token step ----------
+    def _spec_step(self, st: "_SpecState", ngram: int) -> None:
+        """One speculative step with nothing from the host (capturable, in the style of
+        _device_step): the drafts from the rows' own tokens (spec_draft), the last token and the k
+        drafts fed at the positions cache.length + i through the layers' cached decode path (the
+        append at cache.length, then the decode kernel on k + 1 query rows), ln and lm_head, then
+        spec_accept, which chooses the k + 1 tokens, keeps the accepted run, and advances count,
+        held, done and cache.length itself (cache.advance is not called: the rows advance by
+        different amounts, known on the device only). The rejected drafts' K / V rows stay past
+        cache.length: never read, overwritten by the next step's append."""
+        import torch
+        from .tensor import Tensor
+        from .tensor_data import TensorData
+        cache, B, n = st.cache, st.cache.batch_size, st.k + 1
+        # a live row holds at most n_positions - 1 cached tokens (its limit forbids more): only a
+        # finished row can sit higher, and steps back so that its k + 1 discarded rows fit
+        cache.length.clamp_(max=cache.n_positions - n)
+        cache._visible = None
+        self.backend.spec_draft(st.tokens, st.held, st.k, ngram, feed_f32=st.feed_f32, feed_i32=st.feed_i32,
+                                n_draft=st.n_draft)
+        if self.rope is not None:  # the layers read cache.length on the device themselves
+            h = self.token_embeddings(st.feed)
+        else:
+            # only discarded slots (past a row's limit) can pass the last position: they take it
+            pos = (cache.length[:, None] + st.arange[None, :]).clamp_(max=self.n_positions - 1)
+            pos = Tensor(TensorData(pos.to(torch.float32).reshape(-1), (B, n)), backend=self.backend)
+            h = self.token_embeddings(st.feed) + self.position_embeddings(pos)
+        h = self.dropout(h)
+        for i in range(self.n_layer):
+            h = getattr(self, f"t_layer_{i + 1}")(h, None, cache.layer(i))
+        h = self.ln(h.view(B * n, self.n_embd))
+        logits = self.lm_head(h).view(B, n, self.n_vocab)
+        self.backend.spec_accept(logits, st.feed_i32, st.n_draft, st.limit, st.count, st.held, st.done, st.tokens,
+                                 st.history, scratch=st.scratch, cache_len=cache.length, drafted=st.drafted,
+                                 accepted=st.accepted, steps=st.steps, temperature=st.temperature, top_k=st.top_k,
+                                 seed_dev=st.seed, eos_id=st.eos_id)
+
+    def _generate_spec(self, prompts, max_new_tokens, eos_id, sampler, sync_every, prefill_chunk, kv_dtype,
+                       page_size, k, ngram, graph):
+        import torch
+        from .graphs import StepGraph
+        if not self.use_flash_attention:
+            raise ValueError("a KV cache needs use_flash_attention=True")
+        B = len(prompts)
+        lens = np.array([len(p) for p in prompts], dtype=np.int64)
+        new = [[] for _ in range(B)]
+        self.spec_stats = dict(steps=0, tokens=0, drafted=0, accepted=0)
+        if max_new_tokens <= 0:
+            return new
+        temperature, top_k, seed = sampler
+        final = n_pages = None
+        if page_size is not None:
+            # the k + 1 rows a step appends are reserved up front too, a finished row's included, so
+            # that the table is final before the first step (as the graph path reserves its own)
+            final = self._paged_budget(lens, max_new_tokens, page_size, graph=graph)[0]
+            final = np.minimum(final + k + 1, -(-(self.n_positions + k) // page_size) * page_size)
+            n_pages = int((-(-final // page_size)).sum())
+        entry = None
+        if graph:
+            graphs = self.__dict__.setdefault("_decode_graphs", {})
+            slot = ("spec", B, k, kv_dtype, page_size, n_pages)  # the buffers depend on k (the cache's rows)
+            entry = graphs.pop(slot, None)
+            if entry is None:
+                while len(graphs) >= self.MAX_DECODE_BATCH_SIZES:
+                    graphs.pop(next(iter(graphs)))
+                entry = {"state": _SpecState(self, B, k, kv_dtype, page_size, n_pages), "graphs": {}}
+            graphs[slot] = entry  # most recently used last
+            st = entry["state"]
+        else:
+            st = _SpecState(self, B, k, kv_dtype, page_size, n_pages)
+        st.begin(temperature, top_k, eos_id, seed)
+        if page_size is not None:
+            st.cache.reserve(final)
+        # eager, as without speculation: the prefill and the first token (token number 0: the base seed)
+        T = int(lens.max())
+        idx = np.zeros((B, T), dtype=datatype)
+        for b, p in enumerate(prompts):
+            idx[b, :len(p)] = p
+        logits, rows = self._prefill_logits(idx, lens, st.cache, prefill_chunk)
+        self.backend.select_token(logits, temperature, top_k, rows=rows, seed_dev=st.seed, eos_id=st.eos_id,
+                                  out=st.ids_dev, out_i32=st.ids_i32, done=st.done, history=st.history,
+                                  step_dev=st.step)
+        # tokens row b can still return: max_new_tokens, or until it holds more than n_positions
+        limit = np.minimum(max_new_tokens, self.n_positions - lens + 1)
+        st.start(idx, lens, limit)
+        # the steps advance the device lengths only; the host mirror stays where the layers' checks
+        # of it hold for every step (k + 1 rows fit) and is re-synchronised after the loop
+        cache = st.cache
+        np.minimum(cache.length_host, self.n_positions - 1, out=cache.length_host)
+        cache._visible = None
+        total = int(limit.max()) - 1  # every live row emits at least one token per step
+        if total > 0:
+            me = weakref.ref(self)  # no model <-> step-function cycle (see _generate_graph)
+            step = lambda: me()._spec_step(st, ngram)  # noqa: E731
+            if graph:
+                args = (temperature, top_k, st.eos_id, k, ngram)
+                params = tuple(p.value._tensor.data_ptr() for p in self.parameters())
+                held = entry["graphs"].pop(args, None)
+                if held is not None and held[1] == params:
+                    step_graph = held[0]
+                else:
+                    held = None  # a stale graph's memory goes first
+                    while len(entry["graphs"]) >= self.MAX_DECODE_GRAPHS:
+                        entry["graphs"].pop(next(iter(entry["graphs"])))
+                    saved = st.snapshot()
+                    step_graph = StepGraph(step, warmup=2)  # warm-ups: real steps
+                    st.restore(saved)
+                    self.graph_captures = (self.graph_captures or 0) + 1
+                entry["graphs"][args] = (step_graph, params)  # most recently used last
+                step = step_graph.replay
+            for n in range(1, total + 1):
+                step()
+                if n % sync_every == 0 and n < total and bool(st.done.cpu().numpy().all()):
+                    break
+        count = st.count.cpu().numpy()
+        hist = st.history[:, :int(count.max())].cpu().numpy()
+        stats = torch.stack((st.steps, st.drafted, st.accepted)).cpu().numpy()
+        cache.length_host[:] = cache.length.cpu().numpy()
+        cache._visible = None
+        self.spec_stats = dict(steps=int(stats[0].max()), tokens=int(count.sum()), drafted=int(stats[1].sum()),
+                               accepted=int(stats[2].sum()))
+        for b in range(B):
+            for tok in hist[b, :count[b]]:
+                if eos_id is not None and int(tok) == eos_id:
+                    break
+                new[b].append(int(tok))
+                if len(new[b]) >= max_new_tokens or lens[b] + len(new[b]) > self.n_positions:
+                    break
+        return new
+
 
 class _DecodeState:
     """The device buffers of DecoderLM's captured decode step, for one batch size: the KVCache,
@@ -851,11 +1013,11 @@ class _DecodeState:
     flags, the token history [B, n_positions] (no row returns more tokens than that), the step
     counter and the seed slot."""
 
-    def __init__(self, lm: DecoderLM, batch_size: int, kv_dtype=None, page_size=None, n_pages=None):
+    def __init__(self, lm: DecoderLM, batch_size: int, kv_dtype=None, page_size=None, n_pages=None, cache=None):
         import torch
         from .tensor import Tensor
         from .tensor_data import TensorData
-        self.cache = lm.new_cache(batch_size, kv_dtype, page_size, n_pages)
+        self.cache = lm.new_cache(batch_size, kv_dtype, page_size, n_pages) if cache is None else cache
         self.ids_dev = torch.zeros(batch_size, dtype=torch.float32, device="cuda")
         self.ids = Tensor(TensorData(self.ids_dev, (batch_size, 1)), backend=lm.backend)
         self.ids_i32 = torch.zeros(batch_size, dtype=torch.int32, device="cuda")
@@ -891,3 +1053,65 @@ class _DecodeState:
         self.done.copy_(done)
         self.step.copy_(step)
         self.seed.copy_(seed)
+
+
+class _SpecState(_DecodeState):
+    """_DecodeState for DecoderLM's speculative step with k drafts: a cache of n_positions + k rows
+    (the k + 1 rows a step appends fit whatever the row holds; an emitted token never sits at a
+    position >= n_positions, its limit forbids it), the rows' tokens [B, S] (prompt and everything
+    emitted, S = n_positions + 1), the per-row counters the accept kernel advances (count, held,
+    limit; drafted, accepted, steps), the fed tokens [B, k + 1] (fp32, what mt_embedding_fw reads,
+    and int32), the draft counts and the scratch of chosen ids. `seed` holds the call's base seed
+    throughout: token number t draws with seed + t."""
+
+    def __init__(self, lm: DecoderLM, batch_size: int, k: int, kv_dtype=None, page_size=None, n_pages=None):
+        import torch
+        from .kv_cache import KVCache, PagedKVCache
+        from .tensor import Tensor
+        from .tensor_data import TensorData
+        args = (lm.n_layer, batch_size, lm.n_head, lm.n_positions + k, lm.n_embd // lm.n_head, lm.backend)
+        if page_size is not None:
+            cache = PagedKVCache(*args, n_kv_head=lm.n_kv_head, page_size=page_size, n_pages=n_pages)
+        else:
+            cache = KVCache(*args, n_kv_head=lm.n_kv_head, kv_dtype=kv_dtype)
+        super().__init__(lm, batch_size, cache=cache)
+        B, n = batch_size, k + 1
+        self.k = k
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device="cuda")  # noqa: E731
+        self.tokens = i32(B, max(lm.n_positions + 1, k + 2))
+        self.count, self.held, self.limit, self.n_draft = i32(B), i32(B), i32(B), i32(B)
+        self.drafted, self.accepted, self.steps = i32(B), i32(B), i32(B)
+        self.feed_i32, self.scratch = i32(B, n), i32(B, n)
+        self.feed_f32 = torch.zeros(B * n, dtype=torch.float32, device="cuda")
+        self.feed = Tensor(TensorData(self.feed_f32, (B, n)), backend=lm.backend)
+        self.arange = torch.arange(n, dtype=torch.int32, device="cuda")
+
+    def start(self, idx, lens, limit) -> None:
+        """After the prefill and the first token (in ids_i32; done holds its eos flag): the rows'
+        tokens are the prompts idx [B, T] (lens[b] each) and that token, count = 1, held = lens + 1;
+        a row whose limit is 1 is done; the counters start at 0."""
+        import torch
+        B, T = idx.shape
+        host = np.zeros(tuple(self.tokens.shape), dtype=np.int32)
+        host[:, :T] = idx
+        self.tokens.copy_(torch.from_numpy(host))
+        at = torch.from_numpy(np.asarray(lens, dtype=np.int64)).to("cuda")
+        self.tokens[torch.arange(B, device="cuda"), at] = self.ids_i32
+        self.count.fill_(1)
+        self.held.copy_(torch.from_numpy(np.asarray(lens + 1, dtype=np.int32)))
+        self.limit.copy_(torch.from_numpy(np.asarray(limit, dtype=np.int32)))
+        self.done |= (self.limit <= 1).to(torch.int32)
+        for t in (self.drafted, self.accepted, self.steps):
+            t.zero_()
+
+    def snapshot(self):
+        return super().snapshot(), tuple(t.clone() for t in (self.count, self.held, self.drafted, self.accepted,
+                                                             self.steps))
+
+    def restore(self, saved) -> None:
+        # the tokens and the history a warm-up step wrote lie at or past held / count: the replayed
+        # steps write the same values there again
+        base, mine = saved
+        super().restore(base)
+        for t, s in zip((self.count, self.held, self.drafted, self.accepted, self.steps), mine):
+            t.copy_(s)

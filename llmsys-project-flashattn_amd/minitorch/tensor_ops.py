@@ -144,5 +144,9 @@ class TensorBackend:
         self.kv_cache_gather_paged = getattr(ops, "kv_cache_gather_paged", None)
         # the next token chosen on the device (optional: a backend without it keeps the host argmax)
         self.select_token = getattr(ops, "select_token", None)
+        # speculative decoding: drafts and their verification on the device (optional:
+        # generate(speculate=...) needs them)
+        self.spec_draft = getattr(ops, "spec_draft", None)
+        self.spec_accept = getattr(ops, "spec_accept", None)
         # rotary position embedding as one kernel (optional: a backend without it runs the tensor-op form)
         self.rope = getattr(ops, "rope", None)

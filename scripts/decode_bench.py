@@ -99,6 +99,17 @@ PagedKVCaches holding a ragged batch of one row of 4096 tokens and seven of 64.
   generate     generate(graph=True) tokens/s with pos_encoding="rope" against "learned", batch 1 and 8,
                 at the sizes of the graph legs, alternated inside every round
 
+--spec-legs instead writes profiles/spec_bench.json (speculative decoding):
+
+  verify       mt_flash_attn_decode on k + 1 = 2, 4, 8 query rows against the one-row step at (8,16,4096,64),
+                fp32 cache, every leg a captured graph over rotated cache sets
+  draft_accept mt_spec_draft + mt_spec_accept alone (B = 8, V = 10000, rows of 1025 tokens, k = 1, 3, 7), as a
+                captured graph, beside mt_select_token on [B, V]
+  generate     generate(graph=True) tokens/s with speculate in {2, 4, 7} against speculate=None on the same
+                model, batch 1 and 8, with the acceptance rate and the tokens per row and step of each leg: a
+                rotary model over a 97-token vocabulary, whose greedy continuation falls into cycles, and
+                random prompts over 10000 tokens (next to nothing is accepted: the overhead)
+
 No gate: what is measured is recorded.
 """
 import argparse
@@ -944,8 +955,172 @@ def rope_legs(args, torch, minitorch, _hip):
         json.dump(res, f, indent=1)
 
 
+def _graph_of(torch, fn, inner):
+    """`inner` calls of fn(i) as one captured graph (after one eager pass); returns a leg for _timed."""
+    for i in range(inner):
+        fn(i)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for i in range(inner):
+            fn(i)
+    return lambda i: g.replay()
+
+
+def bench_spec_verify(torch, _hip, B, H, L, d, rounds, warmup, inner=16):
+    """The attention of a verify step: mt_flash_attn_decode on k + 1 = 2, 4, 8 query rows per
+    (batch, head) against the one-row step, fp32 cache, every leg a captured graph of `inner`
+    launches over rotated cache sets (as bench_shape rotates them); the legs alternate."""
+    kv_bytes = 2 * B * H * L * d * 4
+    nset = min(8, max(2, -(-2 * ICACHE // kv_bytes) + 1))
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rnd = lambda *s: torch.randn(*s, generator=g, device="cuda", dtype=torch.float32)  # noqa: E731
+    caches = [(rnd(B, L, H, d).permute(0, 2, 1, 3), rnd(B, L, H, d).permute(0, 2, 1, 3)) for _ in range(nset)]
+    kvl = torch.full((B,), L, dtype=torch.int32, device="cuda")
+    legs, plans = {}, {}
+    for nq in (1, 2, 4, 8):
+        q = rnd(B, nq, H, d).permute(0, 2, 1, 3)
+        o = torch.empty((B, nq, H, d), dtype=torch.float32, device="cuda").permute(0, 2, 1, 3)
+        m, l = (torch.empty((B, H, nq), dtype=torch.float32, device="cuda") for _ in range(2))
+        ws_bytes = _hip.decode_workspace_bytes(0, B, H, nq, L, d)
+        ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device="cuda") if ws_bytes else None
+        plans[nq] = _hip.decode_splits(0, B, H, nq, L, d)[0]
+
+        def decode(i, q=q, o=o, m=m, l=l, ws=ws):
+            kc, vc = caches[i % nset]
+            _hip.flash_decode(q, kc, vc, kv_len=kvl, causal=True, out=o, m=m, l=l, workspace=ws)
+        legs[nq] = _graph_of(torch, decode, inner)
+    for fn in legs.values():
+        for _ in range(warmup):
+            _timed(torch, fn, 4)
+    times = {k: [] for k in legs}
+    for r in range(rounds):
+        for k in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            times[k].append(_timed(torch, legs[k], 4) / inner)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    return {"shape": [B, H, L, d], "dtype": "f32", "rounds": rounds, "launches_per_graph": inner,
+            "cache_sets_rotated": nset, "splits": plans,
+            **{f"decode_nq{k}_s_median": v for k, v in med.items()},
+            **{f"decode_nq{k}_s_min": min(v) for k, v in times.items()},
+            **{f"nq{k}_over_nq1": med[k] / med[1] for k in (2, 4, 8)}}
+
+
+def bench_spec_kernels(torch, _hip, B, V, S, k, rounds, warmup, inner=32):
+    """mt_spec_draft + mt_spec_accept alone (the step's overhead beside the model): a captured
+    graph of `inner` draft + accept pairs over rows of S tokens and [B, k + 1, V] logits, greedy
+    and top-k sampling, against mt_select_token on [B, V] (what a one-token step pays)."""
+    g = torch.Generator(device="cuda").manual_seed(0)
+    n = k + 1
+    logits = 3.0 * torch.randn(B, n, V, generator=g, device="cuda", dtype=torch.float32)
+    tokens = torch.randint(0, 50, (B, S), generator=g, device="cuda", dtype=torch.int32)
+    i32 = lambda *s, v=0: torch.full(s, v, dtype=torch.int32, device="cuda")  # noqa: E731
+    st = dict(held=i32(B, v=S - n - 1), count=i32(B, v=1), limit=i32(B, v=1 << 30), done=i32(B),
+              history=i32(B, S), scratch=i32(B, n), feed_i32=i32(B, n), n_draft=i32(B),
+              feed_f32=torch.zeros(B * n, dtype=torch.float32, device="cuda"), cache=i32(B), a=i32(B), dr=i32(B))
+    seed = torch.zeros(1, dtype=torch.int64, device="cuda")
+    out, out_i = torch.empty(B, dtype=torch.float32, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda")
+    kinds = {"greedy": dict(temperature=0.0), "top_k_50": dict(temperature=1.0, top_k=50)}
+
+    def pair(i, kw):
+        # the rows' state is put back first (two tiny fills), so that every pair does the same work
+        st["held"].fill_(S - n - 1)
+        st["count"].fill_(1)
+        _hip.spec_draft(tokens, st["held"], k, 3, feed_f32=st["feed_f32"], feed_i32=st["feed_i32"],
+                        n_draft=st["n_draft"])
+        _hip.spec_accept(logits, st["feed_i32"], st["n_draft"], st["limit"], st["count"], st["held"], st["done"],
+                         tokens, st["history"], scratch=st["scratch"], cache_len=st["cache"], drafted=st["dr"],
+                         accepted=st["a"], seed_dev=seed, **kw)
+    legs = {}
+    for name, kw in kinds.items():
+        legs[f"spec_{name}"] = _graph_of(torch, lambda i, kw=kw: pair(i, kw), inner)
+        legs[f"select_{name}"] = _graph_of(
+            torch, lambda i, kw=kw: _hip.select_token(logits[:, 0], seed_dev=seed, out=out, out_i32=out_i, **kw), inner)
+    for fn in legs.values():
+        for _ in range(warmup):
+            _timed(torch, fn, 4)
+    times = {name: [] for name in legs}
+    for r in range(rounds):
+        for name in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            times[name].append(_timed(torch, legs[name], 4) / inner)
+    return {"B": B, "V": V, "S": S, "k": k, "rounds": rounds, "launches_per_graph": inner,
+            "note": "spec_* = two fills + mt_spec_draft + mt_spec_accept (select over B (k + 1) rows + bookkeeping)",
+            **{f"{name}_s_median": statistics.median(v) for name, v in times.items()},
+            **{f"{name}_s_min": min(v) for name, v in times.items()}}
+
+
+def bench_generate_spec(minitorch, workload, n_positions, prompts, new_tokens, rounds, pos_encoding="learned",
+                        n_vocab=10000):
+    """generate(graph=True) tokens/s with speculate in {2, 4, 7} against speculate=None on the same
+    model, with each leg's acceptance rate (accepted / drafted) and emitted tokens per row and step;
+    the legs alternate inside every round and must return the plain ids."""
+    np.random.seed(0)
+    backend = minitorch.TensorBackend(minitorch.HipKernelOps)
+    lm = minitorch.DecoderLM(n_vocab=n_vocab, n_embd=256, n_head=8, n_positions=n_positions, p_dropout=0.0,
+                             backend=backend, use_fused_kernel=True, use_flash_attention=True,
+                             pos_encoding=pos_encoding)
+    batch = len(prompts)
+    legs = {"plain": lambda: lm.generate(prompts, new_tokens, graph=True)}
+    for k in (2, 4, 7):
+        legs[f"speculate_{k}"] = lambda k=k: lm.generate(prompts, new_tokens, graph=True, speculate=k)
+    out, stats = {}, {}
+    for name, fn in legs.items():  # warm-up (captures the graphs)
+        out[name] = fn()
+        stats[name] = dict(lm.spec_stats) if name != "plain" else None
+    rate = {name: [] for name in legs}
+    for _ in range(rounds):
+        for name, fn in legs.items():
+            t0 = time.perf_counter()
+            toks = fn()  # ends in a device-to-host copy: synchronised
+            rate[name].append(sum(len(t) for t in toks) / (time.perf_counter() - t0))
+    med = {name: statistics.median(v) for name, v in rate.items()}
+    res = {"workload": workload, "pos_encoding": pos_encoding, "n_vocab": n_vocab, "n_positions": n_positions,
+           "prompt_len": len(prompts[0]), "new_tokens": new_tokens, "batch": batch, "rounds": rounds,
+           "ids_equal_plain": all(out[name] == out["plain"] for name in legs),
+           "tokens_returned": sum(len(t) for t in out["plain"]),
+           "plain_tokens_per_s_median": med["plain"], "plain_tokens_per_s_best": max(rate["plain"])}
+    for name, s in stats.items():
+        if s is None:
+            continue
+        res[name] = {"tokens_per_s_median": med[name], "tokens_per_s_best": max(rate[name]),
+                     "over_plain": med[name] / med["plain"], **s,
+                     "acceptance_rate": s["accepted"] / s["drafted"] if s["drafted"] else 0.0,
+                     "tokens_per_row_step": (s["tokens"] - batch) / (batch * s["steps"]) if s["steps"] else 0.0}
+    lm.drop_decode_graphs()
+    return res
+
+
+def spec_legs(args, torch, minitorch, _hip):
+    res = {"device": torch.cuda.get_device_name(0), "verify_attention": [], "draft_accept": [], "generate": []}
+    r = bench_spec_verify(torch, _hip, 8, 16, 4096, 64, args.rounds, args.warmup)
+    print(json.dumps(r), flush=True)
+    res["verify_attention"].append(r)
+    torch.cuda.empty_cache()
+    for k in (1, 3, 7):
+        r = bench_spec_kernels(torch, _hip, 8, 10000, 1025, k, args.rounds, args.warmup)
+        print(json.dumps(r), flush=True)
+        res["draft_accept"].append(r)
+    rng = np.random.default_rng(0)
+    # a workload whose greedy continuation loops: a randomly initialised rotary model over a
+    # 97-token vocabulary falls into short cycles (what it accepts is recorded); and one whose
+    # drafts are (nearly) never right: random prompts over 10000 tokens, the overhead
+    small = [[int(t) for t in rng.integers(0, 97, 64)] for _ in range(8)]
+    rand = [[int(t) for t in rng.integers(0, 10000, 64)] for _ in range(8)]
+    for workload, prompts, enc, n_vocab in (("looping continuation", small[:1], "rope", 97),
+                                            ("looping continuation", small, "rope", 97),
+                                            ("random prompt", rand[:1], "learned", 10000),
+                                            ("random prompt", rand, "learned", 10000)):
+        r = bench_generate_spec(minitorch, workload, 1024, prompts, 256, 3, pos_encoding=enc, n_vocab=n_vocab)
+        print(json.dumps(r), flush=True)
+        res["generate"].append(r)
+    os.makedirs(os.path.dirname(args.spec_out), exist_ok=True)
+    with open(args.spec_out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--spec-legs", action="store_true",
+                    help="run the speculative-decoding legs instead, into --spec-out")
+    ap.add_argument("--spec-out", default=os.path.join(ROOT, "profiles", "spec_bench.json"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "decode_bench.json"))
     ap.add_argument("--graph-legs", action="store_true",
                     help="run the generate(graph=True) and select_token legs instead, into --graph-out")
@@ -981,6 +1156,8 @@ def main():
     from minitorch import _hip
     if args.lib:
         _hip.use_library(os.path.abspath(args.lib), allow_missing=True)
+    if args.spec_legs:
+        return spec_legs(args, torch, minitorch, _hip)
     if args.extend_src_legs:
         return extend_src_legs(args, torch, _hip)
     if args.graph_legs:
