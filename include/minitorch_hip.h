@@ -388,6 +388,33 @@ int mt_select_token(const float* logits, int64_t B, int64_t V, int64_t row_strid
                     float* next_f32, int32_t* next_i32, int32_t* done, int32_t* history,
                     int64_t history_stride, const int32_t* step_dev, void* stream);
 
+/* mt_select_token_p: mt_select_token with two more filters on the kept set, applied after
+ * temperature and top_k in the usual order (temperature, top-k, top-p, min-p). Everything above
+ * holds; mt_select_token is this entry at top_p = 1, min_p = 0, where the launch is the same one.
+ * With e_i = exp((x_i - max_K x) / T) in fp32 for i in K (so the largest is exactly 1), and K
+ * taken in the order (e_i descending, index ascending) - K's own order, except that logits so
+ * close that their e_i round to one fp32 value count as equal:
+ *   top_p in (0, 1], 1 is off: N is the shortest prefix of K whose mass reaches top_p times the
+ *     mass of K. Entries equal in value at the boundary enter in index order, only as many as
+ *     are needed (top_k's tie rule). N always holds the first entry of K. The mass of an entry
+ *     is the integer trunc(e_i 2^40) and the target the fp64 product rounded up, so the prefix
+ *     is exact integer arithmetic; an entry of e_i < 2^-40 weighs nothing and is never needed.
+ *   min_p in [0, 1], 0 is off: M is the entries of K with e_i >= min_p, that is
+ *     p_i >= min_p p_max. All ties stay; M is a prefix of K's order too.
+ *   The kept set is N intersected with M, the shorter of the two prefixes; p is renormalised
+ *   over it, and the id is the first kept i, in index order, whose running sum exceeds u times
+ *   the kept total (the fallback is mt_select_token's: the last kept index with p > 0).
+ *   temperature == 0 (greedy) ignores both, as it ignores top_k, and a row whose maximum is not
+ *   finite takes the greedy id.
+ * The id is a function of the row's bits, T, top_k, top_p, min_p, the seed and b alone: every
+ * sum has a fixed order or is an exact integer sum (no floating-point atomics).
+ * Refused with a status before any device call: top_p NaN, <= 0 or > 1; min_p NaN, < 0 or > 1;
+ * whatever mt_select_token refuses. */
+int mt_select_token_p(const float* logits, int64_t B, int64_t V, int64_t row_stride, float temperature,
+                      int64_t top_k, float top_p, float min_p, uint64_t seed, const uint64_t* seed_dev,
+                      int64_t eos_id, float* next_f32, int32_t* next_i32, int32_t* done, int32_t* history,
+                      int64_t history_stride, const int32_t* step_dev, void* stream);
+
 /* ---- speculative decoding: prompt-lookup drafts, verified on the device ------
  * Both entries are stream-ordered, allocate nothing, do not synchronise, write with plain stores
  * and are capturable in a hipGraph; their launches depend on the sizes alone.
@@ -428,7 +455,12 @@ int mt_select_token(const float* logits, int64_t B, int64_t V, int64_t row_strid
  * nothing reads them and the next step overwrites them.
  * Refused with a status before any device call: k outside 1..7, B, V or S <= 0, V > 32768,
  * S < k + 2, row_stride < V, batch_stride < k row_stride + V, token_stride < S, history_stride
- * <= 0, a negative or NaN temperature, a NULL required pointer. */
+ * <= 0, a negative or NaN temperature, a NULL required pointer.
+ *
+ * mt_spec_accept_p: mt_spec_accept whose step 1 chooses c_i by mt_select_token_p's rule (top_p,
+ * min_p after top_k; the same kernel), so that speculative ids stay those of the non-speculative
+ * call; mt_spec_accept is this entry at top_p = 1, min_p = 0. It also refuses top_p NaN, <= 0 or
+ * > 1 and min_p NaN, < 0 or > 1. */
 int mt_spec_draft(const int32_t* tokens, int64_t B, int64_t S, int64_t token_stride, const int32_t* held,
                   int64_t k, int64_t max_ngram, float* feed_f32, int32_t* feed_i32, int32_t* n_draft,
                   void* stream);
@@ -439,6 +471,13 @@ int mt_spec_accept(const float* logits, int64_t B, int64_t k, int64_t V, int64_t
                    int32_t* drafted, int32_t* accepted, int32_t* steps, int32_t* tokens, int64_t S,
                    int64_t token_stride, int32_t* history, int64_t history_stride, int32_t* scratch,
                    void* stream);
+int mt_spec_accept_p(const float* logits, int64_t B, int64_t k, int64_t V, int64_t batch_stride,
+                     int64_t row_stride, const int32_t* feed_i32, const int32_t* n_draft, float temperature,
+                     int64_t top_k, float top_p, float min_p, uint64_t seed, const uint64_t* seed_dev,
+                     int64_t eos_id, const int32_t* limit, int32_t* count, int32_t* held, int32_t* cache_len,
+                     int32_t* done, int32_t* drafted, int32_t* accepted, int32_t* steps, int32_t* tokens,
+                     int64_t S, int64_t token_stride, int32_t* history, int64_t history_stride,
+                     int32_t* scratch, void* stream);
 
 /* ---- rotary position embedding (RoPE) ---------------------------------------
  * The head rows of x [B, H, T, d] rotated by their positions, in the half-split ("rotate-half")

@@ -32,9 +32,16 @@ struct SelectArgs {
   const int32_t* count;
   const int32_t* skip;
   int32_t* scratch;
+  // mt_select_token_p / mt_spec_accept_p: the nucleus and min-p filters (1 and 0: off). Last, so
+  // that the kernel without the phase reads what it read before they were added.
+  float top_p, min_p;
 };
 
-// one workgroup per logits row: B * a.rows of them
+// one workgroup per logits row: B * a.rows of them. A sampling launch with top_p < 1 or min_p > 0
+// runs select_token_kernel<CAP, true> (the nucleus phase compiled in), every other one
+// select_token_kernel<CAP, false>, whose instructions are those of the kernel before the phase.
 hipError_t launch_select(const SelectArgs& a, int64_t B, hipStream_t st);
+// the shared refusal of both _p entries: top_p outside (0, 1], min_p outside [0, 1], a NaN
+int check_nucleus(const char* who, float top_p, float min_p);
 
 }  // namespace mt

@@ -19,8 +19,19 @@
 //      entries, tiles of zeros skipped) from the total of the quarters before it and reports
 //      the first entry whose running sum exceeds u * sum; the lowest such index wins, and the
 //      last kept index with e_i > 0 when rounding leaves none.
-// Every sum has a fixed association, so the id is a function of the row's bits, T, top_k, the
-// seed and b alone. Stores are plain vector stores; the only atomics are on the LDS histogram.
+//  2p. mt_select_token_p / mt_spec_accept_p with top_p < 1 or min_p > 0 only (the NUCLEUS
+//      instantiation; every other launch runs the kernel without this phase, whose device code
+//      is what it was before the phase existed): the e_i are non-negative, so their bit patterns
+//      order as unsigned integers. top_p: the bit pattern of the last entry of the nucleus by
+//      the radix select of phase 1 on mass instead of count (the mass of an entry is the integer
+//      trunc(e_i 2^40), summed per bin by 64-bit LDS integer atomics: exact, so independent of
+//      their order), and the tie cut among the entries equal to it by the ballot walk of phase
+//      1 (tie_cut below; phase 1 keeps its own copy of the walk so that its code stays as it
+//      was). min_p: e_i >= min_p. What falls outside either is zeroed and the wave totals are
+//      formed again in phase 2's order.
+// Every sum has a fixed association or is an exact integer sum, so the id is a function of the
+// row's bits, T, top_k, top_p, min_p, the seed and b alone. Stores are plain vector stores; the
+// only atomics are integer ones on the LDS histograms.
 // mt_spec_accept (spec_decode.hip) launches the same kernel over k + 1 logits rows per batch row
 // (select_token.h: SelectArgs.rows, count, skip, scratch): row i of batch row b draws with
 // seed + count[b] + i and b's uniform, and its id goes to the caller's scratch only.
@@ -60,7 +71,40 @@ __device__ __forceinline__ void write_id(const SelectArgs& a, int b, int i, int 
   }
 }
 
-template <int CAP>
+// The index of the `need`-th entry, in index order, for which is_tie holds (1 <= need <= their
+// number): each wave counts its quarter [lo, hi) by ballots, the one that holds it walks it again.
+// Two barriers; every thread of the workgroup calls it.
+template <class F>
+__device__ __forceinline__ int tie_cut(F is_tie, int lo, int hi, int need, int lane, int wave, int* ties_w,
+                                       int* cut_s) {
+  int cnt = 0;
+  for (int t = lo; t < hi; t += 64) {
+    const int i = t + lane;
+    cnt += __popcll(__ballot(i < hi && is_tie(i)));
+  }
+  if (lane == 0) ties_w[wave] = cnt;
+  __syncthreads();
+  int run = 0;
+  for (int w = 0; w < wave; ++w) run += ties_w[w];
+  if (run < need && need <= run + cnt) {
+    for (int t = lo; t < hi; t += 64) {
+      const int i = t + lane;
+      unsigned long long m = __ballot(i < hi && is_tie(i));
+      const int c = __popcll(m);
+      if (run + c >= need) {
+        for (int q = need - run; q > 1; --q) m &= m - 1;
+        if (lane == 0) *cut_s = t + __ffsll((long long)m) - 1;
+        break;
+      }
+      run += c;
+    }
+  }
+  __syncthreads();
+  return *cut_s;
+}
+
+// NUCLEUS: the top-p / min-p phase between phases 2 and 3; false is the kernel without it
+template <int CAP, bool NUCLEUS>
 __global__ __launch_bounds__(kSelThreads) void select_token_kernel(const SelectArgs a) {
   __shared__ __attribute__((aligned(16))) float row[CAP];
   __shared__ __attribute__((aligned(16))) unsigned hist[256];
@@ -229,6 +273,101 @@ __global__ __launch_bounds__(kSelThreads) void select_token_kernel(const SelectA
   for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
   if (lane == 0) { sum_w[wave] = lsum; last_w[wave] = last; }
   __syncthreads();
+
+  // ---- 2p: top-p and min-p over the e_i ----------------------------------------------------
+  // The e_i are >= 0 and <= 1, so their bit patterns order as unsigned integers and are below
+  // 2^30: the key is the pattern shifted left by 2 (the first 8-bit digit then spreads over the
+  // low exponent bits). N: key > tp, or key == tp and index <= pcut; M: e_i >= min_p.
+  if constexpr (NUCLEUS) {
+    __shared__ __attribute__((aligned(16))) unsigned long long mass[256];
+    __shared__ unsigned long long need_s;
+    unsigned tp = 0;
+    int pcut = V - 1;
+    if (a.top_p < 1.f) {
+      // The threshold by the radix select of phase 1 on mass instead of count: the mass of an
+      // entry is the integer q_i = trunc(e_i 2^40) <= 2^40, so a bin's mass (below 2^55) does not
+      // depend on the order of the atomics. Entries of q = 0 (e_i < 2^-40) weigh nothing.
+      unsigned prefix = 0;
+      unsigned long long need = 0;
+      for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        mass[tid] = 0;
+        __syncthreads();
+        for (int i0 = 4 * tid; i0 < V; i0 += 4 * kSelThreads) {
+          const float4 v = *(const float4*)&row[i0];
+          const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (i0 + j >= V) continue;
+            const unsigned key = __float_as_uint(x[j]) << 2;
+            const unsigned long long q = (unsigned long long)(x[j] * 0x1p40f);
+            if (q != 0 && (pass == 0 || (key >> (shift + 8)) == prefix)) atomicAdd(&mass[(key >> shift) & 255u], q);
+          }
+        }
+        __syncthreads();
+        if (wave == 0) {
+          // lane l owns bins 4l .. 4l+3; `above`: the mass in higher bins
+          const unsigned long long h[4] = {mass[4 * lane], mass[4 * lane + 1], mass[4 * lane + 2], mass[4 * lane + 3]};
+          const unsigned long long s4 = h[0] + h[1] + h[2] + h[3];
+          unsigned long long suf = s4;
+          for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long t = __shfl_down(suf, o, 64);
+            if (lane + o < 64) suf += t;
+          }
+          if (pass == 0) {
+            // the smallest integer mass that reaches top_p Q, Q = sum of all q_i >= 2^40
+            const unsigned long long Q = __shfl(suf, 0, 64);
+            const double want = ceil((double)a.top_p * (double)Q);
+            need = want < 1.0 ? 1ull : (unsigned long long)want;
+            need = need > Q ? Q : need;
+          }
+          unsigned long long above = suf - s4;
+#pragma unroll
+          for (int j = 3; j >= 0; --j) {
+            if (above < need && need <= above + h[j]) {  // exactly one (lane, j)
+              sel[0] = 4u * lane + j;
+              need_s = need - above;
+            }
+            above += h[j];
+          }
+        }
+        __syncthreads();
+        prefix = (prefix << 8) | sel[0];
+        need = need_s;
+      }
+      tp = prefix;
+      // every entry of the threshold's class weighs qt: the first n_need of them, in index order
+      const unsigned long long qt = (unsigned long long)(__uint_as_float(tp >> 2) * 0x1p40f);
+      const unsigned long long n_need = (need + qt - 1) / qt;
+      if (n_need * qt != mass[tp & 255u])
+        pcut = tie_cut([&](int i) { return __float_as_uint(row[i]) == (tp >> 2); }, lo, hi, (int)n_need, lane, wave,
+                       ties_w, &cut_s);
+    }
+    // zero what falls outside N and M; the wave totals again, in phase 2's order
+    const unsigned tpb = tp >> 2;
+    const float floor_e = a.min_p;
+    lsum = 0.f;
+    last = -1;
+    for (int t = lo; t < hi; t += 256) {
+      const int i0 = t + 4 * lane;
+      float4 v = *(const float4*)&row[i0];
+      float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int i = i0 + j;
+        const unsigned bits = __float_as_uint(e[j]);
+        const bool keep = (bits > tpb || (bits == tpb && i <= pcut)) && e[j] >= floor_e;
+        e[j] = keep ? e[j] : 0.f;
+        lsum += e[j];
+        last = e[j] > 0.f ? i : last;
+      }
+      *(float4*)&row[i0] = make_float4(e[0], e[1], e[2], e[3]);
+    }
+    lsum = wave_sum(lsum);
+    for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+    if (lane == 0) { sum_w[wave] = lsum; last_w[wave] = last; }
+    __syncthreads();
+  }
   float total = 0.f, run = 0.f;
   for (int w = 0; w < 4; ++w) {
     if (w == wave) run = total;
@@ -274,33 +413,48 @@ __global__ __launch_bounds__(kSelThreads) void select_token_kernel(const SelectA
 
 hipError_t launch_select(const SelectArgs& a, int64_t B, hipStream_t st) {
   const dim3 grid((unsigned)(B * a.rows)), block(kSelThreads);
-  if (a.V <= 4096) select_token_kernel<4096><<<grid, block, 0, st>>>(a);
-  else if (a.V <= 16384) select_token_kernel<16384><<<grid, block, 0, st>>>(a);
-  else select_token_kernel<kSelMaxV><<<grid, block, 0, st>>>(a);
+  // greedy ignores both filters; at their off values the kernel without the phase runs
+  if (a.temperature > 0.f && (a.top_p < 1.f || a.min_p > 0.f)) {
+    if (a.V <= 4096) select_token_kernel<4096, true><<<grid, block, 0, st>>>(a);
+    else if (a.V <= 16384) select_token_kernel<16384, true><<<grid, block, 0, st>>>(a);
+    else select_token_kernel<kSelMaxV, true><<<grid, block, 0, st>>>(a);
+    return hipGetLastError();
+  }
+  if (a.V <= 4096) select_token_kernel<4096, false><<<grid, block, 0, st>>>(a);
+  else if (a.V <= 16384) select_token_kernel<16384, false><<<grid, block, 0, st>>>(a);
+  else select_token_kernel<kSelMaxV, false><<<grid, block, 0, st>>>(a);
   return hipGetLastError();
+}
+
+// top_p in (0, 1], min_p in [0, 1]; a NaN fails both
+int check_nucleus(const char* who, float top_p, float min_p) {
+  if (!(top_p > 0.f && top_p <= 1.f)) return set_error("%s: top_p must be in (0, 1] (got %g)", who, (double)top_p);
+  if (!(min_p >= 0.f && min_p <= 1.f)) return set_error("%s: min_p must be in [0, 1] (got %g)", who, (double)min_p);
+  return 0;
 }
 }  // namespace mt
 
 using namespace mt;
 
-extern "C" int mt_select_token(const float* logits, int64_t B, int64_t V, int64_t row_stride,
-                               float temperature, int64_t top_k, uint64_t seed, const uint64_t* seed_dev,
-                               int64_t eos_id, float* next_f32, int32_t* next_i32, int32_t* done,
-                               int32_t* history, int64_t history_stride, const int32_t* step_dev,
-                               void* stream) {
-  if (B <= 0 || V <= 0) return set_error("mt_select_token: bad sizes B=%lld V=%lld", (long long)B, (long long)V);
+static int select_token_impl(const char* who, const float* logits, int64_t B, int64_t V, int64_t row_stride,
+                             float temperature, int64_t top_k, float top_p, float min_p, uint64_t seed,
+                             const uint64_t* seed_dev, int64_t eos_id, float* next_f32, int32_t* next_i32,
+                             int32_t* done, int32_t* history, int64_t history_stride, const int32_t* step_dev,
+                             void* stream) {
+  if (B <= 0 || V <= 0) return set_error("%s: bad sizes B=%lld V=%lld", who, (long long)B, (long long)V);
   if (V > kSelMaxV)
-    return set_error("mt_select_token: V=%lld is above the limit of %d (the row is held in LDS)", (long long)V, kSelMaxV);
-  if (B > (1ll << 31) - 1) return set_error("mt_select_token: B=%lld out of range", (long long)B);
+    return set_error("%s: V=%lld is above the limit of %d (the row is held in LDS)", who, (long long)V, kSelMaxV);
+  if (B > (1ll << 31) - 1) return set_error("%s: B=%lld out of range", who, (long long)B);
   if (row_stride < V)
-    return set_error("mt_select_token: row_stride %lld is below V=%lld", (long long)row_stride, (long long)V);
-  if (!(temperature >= 0.f)) return set_error("mt_select_token: temperature must be >= 0 (got %g)", (double)temperature);
-  if (!logits) return set_error("mt_select_token: logits is NULL");
-  if ((uintptr_t)logits & 3) return set_error("mt_select_token: logits is not 4-B aligned");
-  if (!next_f32 && !next_i32) return set_error("mt_select_token: both outputs (next_f32, next_i32) are NULL");
-  if (history && !step_dev) return set_error("mt_select_token: history needs step_dev");
+    return set_error("%s: row_stride %lld is below V=%lld", who, (long long)row_stride, (long long)V);
+  if (!(temperature >= 0.f)) return set_error("%s: temperature must be >= 0 (got %g)", who, (double)temperature);
+  if (!logits) return set_error("%s: logits is NULL", who);
+  if ((uintptr_t)logits & 3) return set_error("%s: logits is not 4-B aligned", who);
+  if (!next_f32 && !next_i32) return set_error("%s: both outputs (next_f32, next_i32) are NULL", who);
+  if (history && !step_dev) return set_error("%s: history needs step_dev", who);
   if (history && history_stride <= 0)
-    return set_error("mt_select_token: history_stride %lld must be positive", (long long)history_stride);
+    return set_error("%s: history_stride %lld must be positive", who, (long long)history_stride);
+  if (check_nucleus(who, top_p, min_p)) return 1;
   SelectArgs a;
   a.logits = logits; a.row_stride = row_stride; a.V = (int)V;
   a.top_k = (int)(top_k <= 0 || top_k >= V ? 0 : top_k);
@@ -308,5 +462,24 @@ extern "C" int mt_select_token(const float* logits, int64_t B, int64_t V, int64_
   a.next_f32 = next_f32; a.next_i32 = next_i32; a.done = done;
   a.history = history; a.history_stride = history_stride; a.step_dev = step_dev;
   a.rows = 1; a.batch_stride = row_stride; a.count = nullptr; a.skip = nullptr; a.scratch = nullptr;
-  return check_hip(launch_select(a, B, (hipStream_t)stream), "mt_select_token");
+  a.top_p = top_p; a.min_p = min_p;
+  return check_hip(launch_select(a, B, (hipStream_t)stream), who);
+}
+
+extern "C" int mt_select_token(const float* logits, int64_t B, int64_t V, int64_t row_stride,
+                               float temperature, int64_t top_k, uint64_t seed, const uint64_t* seed_dev,
+                               int64_t eos_id, float* next_f32, int32_t* next_i32, int32_t* done,
+                               int32_t* history, int64_t history_stride, const int32_t* step_dev,
+                               void* stream) {
+  return select_token_impl("mt_select_token", logits, B, V, row_stride, temperature, top_k, 1.f, 0.f, seed, seed_dev,
+                           eos_id, next_f32, next_i32, done, history, history_stride, step_dev, stream);
+}
+
+extern "C" int mt_select_token_p(const float* logits, int64_t B, int64_t V, int64_t row_stride,
+                                 float temperature, int64_t top_k, float top_p, float min_p, uint64_t seed,
+                                 const uint64_t* seed_dev, int64_t eos_id, float* next_f32, int32_t* next_i32,
+                                 int32_t* done, int32_t* history, int64_t history_stride,
+                                 const int32_t* step_dev, void* stream) {
+  return select_token_impl("mt_select_token_p", logits, B, V, row_stride, temperature, top_k, top_p, min_p, seed,
+                           seed_dev, eos_id, next_f32, next_i32, done, history, history_stride, step_dev, stream);
 }

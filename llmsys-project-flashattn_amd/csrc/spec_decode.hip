@@ -153,38 +153,39 @@ extern "C" int mt_spec_draft(const int32_t* tokens, int64_t B, int64_t S, int64_
   return check_hip(hipGetLastError(), "mt_spec_draft");
 }
 
-extern "C" int mt_spec_accept(const float* logits, int64_t B, int64_t k, int64_t V, int64_t batch_stride,
-                              int64_t row_stride, const int32_t* feed_i32, const int32_t* n_draft,
-                              float temperature, int64_t top_k, uint64_t seed, const uint64_t* seed_dev,
-                              int64_t eos_id, const int32_t* limit, int32_t* count, int32_t* held,
-                              int32_t* cache_len, int32_t* done, int32_t* drafted, int32_t* accepted,
-                              int32_t* steps, int32_t* tokens, int64_t S, int64_t token_stride,
-                              int32_t* history, int64_t history_stride, int32_t* scratch, void* stream) {
-  if (check_k("mt_spec_accept", k)) return 1;
+static int spec_accept_impl(const char* who, const float* logits, int64_t B, int64_t k, int64_t V, int64_t batch_stride,
+                            int64_t row_stride, const int32_t* feed_i32, const int32_t* n_draft, float temperature,
+                            int64_t top_k, float top_p, float min_p, uint64_t seed, const uint64_t* seed_dev,
+                            int64_t eos_id, const int32_t* limit, int32_t* count, int32_t* held,
+                            int32_t* cache_len, int32_t* done, int32_t* drafted, int32_t* accepted,
+                            int32_t* steps, int32_t* tokens, int64_t S, int64_t token_stride,
+                            int32_t* history, int64_t history_stride, int32_t* scratch, void* stream) {
+  if (check_k(who, k)) return 1;
   if (B <= 0 || V <= 0 || S <= 0)
-    return set_error("mt_spec_accept: bad sizes B=%lld V=%lld S=%lld", (long long)B, (long long)V, (long long)S);
+    return set_error("%s: bad sizes B=%lld V=%lld S=%lld", who, (long long)B, (long long)V, (long long)S);
   if (V > kSelMaxV)
-    return set_error("mt_spec_accept: V=%lld is above the limit of %d (the row is held in LDS)", (long long)V, kSelMaxV);
+    return set_error("%s: V=%lld is above the limit of %d (the row is held in LDS)", who, (long long)V, kSelMaxV);
   if (B > ((1ll << 31) - 1) / (k + 1) || S > (1ll << 31) - 1)
-    return set_error("mt_spec_accept: B=%lld S=%lld out of range", (long long)B, (long long)S);
-  if (S < k + 2) return set_error("mt_spec_accept: S=%lld is below k + 2 = %lld", (long long)S, (long long)(k + 2));
+    return set_error("%s: B=%lld S=%lld out of range", who, (long long)B, (long long)S);
+  if (S < k + 2) return set_error("%s: S=%lld is below k + 2 = %lld", who, (long long)S, (long long)(k + 2));
   if (row_stride < V)
-    return set_error("mt_spec_accept: row_stride %lld is below V=%lld", (long long)row_stride, (long long)V);
+    return set_error("%s: row_stride %lld is below V=%lld", who, (long long)row_stride, (long long)V);
   if (batch_stride < k * row_stride + V)
-    return set_error("mt_spec_accept: batch_stride %lld is below the k + 1 = %lld rows of a batch row",
+    return set_error("%s: batch_stride %lld is below the k + 1 = %lld rows of a batch row", who,
                      (long long)batch_stride, (long long)(k + 1));
   if (token_stride < S)
-    return set_error("mt_spec_accept: token_stride %lld is below S=%lld", (long long)token_stride, (long long)S);
+    return set_error("%s: token_stride %lld is below S=%lld", who, (long long)token_stride, (long long)S);
   if (history_stride <= 0)
-    return set_error("mt_spec_accept: history_stride %lld must be positive", (long long)history_stride);
-  if (!(temperature >= 0.f)) return set_error("mt_spec_accept: temperature must be >= 0 (got %g)", (double)temperature);
-  if (!logits) return set_error("mt_spec_accept: logits is NULL");
-  if ((uintptr_t)logits & 3) return set_error("mt_spec_accept: logits is not 4-B aligned");
+    return set_error("%s: history_stride %lld must be positive", who, (long long)history_stride);
+  if (!(temperature >= 0.f)) return set_error("%s: temperature must be >= 0 (got %g)", who, (double)temperature);
+  if (!logits) return set_error("%s: logits is NULL", who);
+  if ((uintptr_t)logits & 3) return set_error("%s: logits is not 4-B aligned", who);
   const struct { const void* p; const char* name; } need[] = {
       {feed_i32, "feed_i32"}, {n_draft, "n_draft"}, {limit, "limit"}, {count, "count"}, {held, "held"},
       {done, "done"}, {tokens, "tokens"}, {history, "history"}, {scratch, "scratch"}};
   for (const auto& q : need)
-    if (!q.p) return set_error("mt_spec_accept: %s is NULL", q.name);
+    if (!q.p) return set_error("%s: %s is NULL", who, q.name);
+  if (check_nucleus(who, top_p, min_p)) return 1;
   SelectArgs s;
   s.logits = logits; s.row_stride = row_stride; s.V = (int)V;
   s.top_k = (int)(top_k <= 0 || top_k >= V ? 0 : top_k);
@@ -192,12 +193,39 @@ extern "C" int mt_spec_accept(const float* logits, int64_t B, int64_t k, int64_t
   s.next_f32 = nullptr; s.next_i32 = nullptr; s.done = nullptr;
   s.history = nullptr; s.history_stride = 0; s.step_dev = nullptr;
   s.rows = (int)(k + 1); s.batch_stride = batch_stride; s.count = count; s.skip = done; s.scratch = scratch;
-  if (check_hip(launch_select(s, B, (hipStream_t)stream), "mt_spec_accept (select)")) return 1;
+  s.top_p = top_p; s.min_p = min_p;
+  if (check_hip(launch_select(s, B, (hipStream_t)stream), who)) return 1;
   AcceptArgs a;
   a.B = (int)B; a.k = (int)k; a.S = (int)S; a.chosen = scratch; a.feed = feed_i32; a.n_draft = n_draft;
   a.limit = limit; a.eos_id = eos_id; a.count = count; a.held = held; a.cache_len = cache_len; a.done = done;
   a.drafted = drafted; a.accepted = accepted; a.steps = steps; a.tokens = tokens; a.token_stride = token_stride;
   a.history = history; a.history_stride = history_stride;
   spec_accept_kernel<<<dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream>>>(a);
-  return check_hip(hipGetLastError(), "mt_spec_accept");
+  return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int mt_spec_accept(const float* logits, int64_t B, int64_t k, int64_t V, int64_t batch_stride,
+                              int64_t row_stride, const int32_t* feed_i32, const int32_t* n_draft,
+                              float temperature, int64_t top_k, uint64_t seed, const uint64_t* seed_dev,
+                              int64_t eos_id, const int32_t* limit, int32_t* count, int32_t* held,
+                              int32_t* cache_len, int32_t* done, int32_t* drafted, int32_t* accepted,
+                              int32_t* steps, int32_t* tokens, int64_t S, int64_t token_stride,
+                              int32_t* history, int64_t history_stride, int32_t* scratch, void* stream) {
+  return spec_accept_impl("mt_spec_accept", logits, B, k, V, batch_stride, row_stride, feed_i32, n_draft, temperature,
+                          top_k, 1.f, 0.f, seed, seed_dev, eos_id, limit, count, held, cache_len, done, drafted,
+                          accepted, steps, tokens, S, token_stride, history, history_stride, scratch, stream);
+}
+
+extern "C" int mt_spec_accept_p(const float* logits, int64_t B, int64_t k, int64_t V, int64_t batch_stride,
+                                int64_t row_stride, const int32_t* feed_i32, const int32_t* n_draft,
+                                float temperature, int64_t top_k, float top_p, float min_p, uint64_t seed,
+                                const uint64_t* seed_dev, int64_t eos_id, const int32_t* limit, int32_t* count,
+                                int32_t* held, int32_t* cache_len, int32_t* done, int32_t* drafted,
+                                int32_t* accepted, int32_t* steps, int32_t* tokens, int64_t S,
+                                int64_t token_stride, int32_t* history, int64_t history_stride, int32_t* scratch,
+                                void* stream) {
+  return spec_accept_impl("mt_spec_accept_p", logits, B, k, V, batch_stride, row_stride, feed_i32, n_draft,
+                          temperature, top_k, top_p, min_p, seed, seed_dev, eos_id, limit, count, held, cache_len,
+                          done, drafted, accepted, steps, tokens, S, token_stride, history, history_stride, scratch,
+                          stream);
 }

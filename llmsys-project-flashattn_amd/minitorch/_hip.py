@@ -93,6 +93,11 @@ _PROTOS = {
                                         _i64p, _i64p, _i64p, _i64p, _vp, _vp, _vp]),
     "mt_select_token": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _i64, ctypes.c_uint64, _vp, _i64,
                                _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "mt_select_token_p": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _i64, ctypes.c_float, ctypes.c_float,
+                                 ctypes.c_uint64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "mt_spec_accept_p": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, ctypes.c_float, _i64, ctypes.c_float,
+                                ctypes.c_float, ctypes.c_uint64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     "mt_spec_draft": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "mt_spec_accept": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, ctypes.c_float, _i64, ctypes.c_uint64,
                               _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp,
@@ -862,13 +867,27 @@ def rand_uniform(n: int, seed: int, out=None, stream: Optional[int] = None):
     return out
 
 
+def _nucleus_entry(name: str, top_p: float, min_p: float):
+    """(the entry `name`_p, True), or (the entry without the filters, False) where a library loaded
+    by use_library(allow_missing=True) predates them and both are at their off values."""
+    fn = getattr(lib(), name + "_p", None)
+    if fn is not None:
+        return fn, True
+    if top_p == 1.0 and min_p == 0.0:
+        return getattr(lib(), name), False
+    raise RuntimeError(f"{LIB_PATH} lacks {name}_p (top_p / min_p): rebuild it")
+
+
 def select_token(logits, temperature: float = 0.0, top_k: int = 0, seed: int = 0, seed_dev=None, eos_id=None,
-                 out=None, out_i32=None, done=None, history=None, step_dev=None, stream: Optional[int] = None):
-    """The next token id of every row of logits (mt_select_token): a 2-D fp32 device view [B, V]
+                 out=None, out_i32=None, done=None, history=None, step_dev=None, stream: Optional[int] = None,
+                 top_p: float = 1.0, min_p: float = 0.0):
+    """The next token id of every row of logits (mt_select_token_p): a 2-D fp32 device view [B, V]
     with a unit-stride last dim and any row stride >= V (e.g. ``logits3d[:, -1]``, no copy).
     temperature 0: greedy (np.argmax's id); > 0: a draw from softmax(logits / temperature) over
-    the top_k largest entries (0: all), with u the value rand_uniform writes at index b for
-    `seed`. seed_dev: a device int64 [1] holding the seed instead (read when the kernel runs).
+    the top_k largest entries (0: all), cut further to the nucleus of mass top_p (1: off) and to
+    the entries of at least min_p times the largest probability (0: off), with u the value
+    rand_uniform writes at index b for `seed`. seed_dev: a device int64 [1] holding the seed
+    instead (read when the kernel runs).
     Returns (out, out_i32): fp32 [B] and int32 [B] ids, allocated when not given. done: int32 [B]
     in/out, done[b] |= (id == eos_id). history: int32 [B, S] with step_dev an int32 [1] on the
     device: history[b, step_dev[0]] = id."""
@@ -902,10 +921,12 @@ def select_token(logits, temperature: float = 0.0, top_k: int = 0, seed: int = 0
             raise ValueError("select_token: history rows must be contiguous")
     ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     st = stream_ptr(logits.device) if stream is None else stream
-    check(lib().mt_select_token(
-        logits.data_ptr(), B, V, row_stride, float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF,
+    fn, filters = _nucleus_entry("mt_select_token", float(top_p), float(min_p))
+    check(fn(
+        logits.data_ptr(), B, V, row_stride, float(temperature), int(top_k),
+        *((float(top_p), float(min_p)) if filters else ()), int(seed) & 0xFFFFFFFFFFFFFFFF,
         ptr(seed_dev), -1 if eos_id is None else int(eos_id), out.data_ptr(), out_i32.data_ptr(), ptr(done),
-        ptr(history), hs, ptr(step_dev), st), "mt_select_token")
+        ptr(history), hs, ptr(step_dev), st), "mt_select_token_p")
     return out, out_i32
 
 
@@ -957,14 +978,16 @@ def spec_draft(tokens, held, k: int, max_ngram: int = 3, feed_f32=None, feed_i32
 
 def spec_accept(logits, feed_i32, n_draft, limit, count, held, done, tokens, history, scratch=None,
                 cache_len=None, drafted=None, accepted=None, steps=None, temperature: float = 0.0, top_k: int = 0,
-                seed: int = 0, seed_dev=None, eos_id=None, stream: Optional[int] = None):
-    """Verify the drafts of one speculative step and do its bookkeeping (mt_spec_accept): logits a
+                seed: int = 0, seed_dev=None, eos_id=None, stream: Optional[int] = None, top_p: float = 1.0,
+                min_p: float = 0.0):
+    """Verify the drafts of one speculative step and do its bookkeeping (mt_spec_accept_p): logits a
     3-D fp32 device view [B, k + 1, V] with unit-stride columns; feed_i32 / n_draft as spec_draft
     wrote them; limit, count, held, done (and the optional cache_len, drafted, accepted, steps)
     int32 [B]; tokens, history int32 [B, S] / [B, S']; scratch int32 [B, k + 1] (allocated when
     None; pass one inside a captured step). seed / seed_dev: the call's base seed (token number
-    count[b] + i draws with base + count[b] + i). Everything is updated in place; returns scratch,
-    which then holds the k + 1 chosen ids of every row that was not done."""
+    count[b] + i draws with base + count[b] + i); top_p / min_p: select_token's. Everything is
+    updated in place; returns scratch, which then holds the k + 1 chosen ids of every row that was
+    not done."""
     torch = _torch()
     who = "spec_accept"
     _check_dev(logits)
@@ -984,14 +1007,16 @@ def spec_accept(logits, feed_i32, n_draft, limit, count, held, done, tokens, his
         raise ValueError(f"{who}: history rows must be contiguous")
     v = lambda name, t, m=B, **kw: _spec_vec(who, name, t, m, **kw)  # noqa: E731
     st = stream_ptr(logits.device) if stream is None else stream
-    check(lib().mt_spec_accept(
+    fn, filters = _nucleus_entry("mt_spec_accept", float(top_p), float(min_p))
+    check(fn(
         logits.data_ptr(), B, k, V, batch_stride, row_stride, v("feed_i32", feed_i32, B * n), v("n_draft", n_draft),
-        float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF,
+        float(temperature), int(top_k), *((float(top_p), float(min_p)) if filters else ()),
+        int(seed) & 0xFFFFFFFFFFFFFFFF,
         v("seed_dev", seed_dev, 1, dtype=torch.int64, optional=True), -1 if eos_id is None else int(eos_id),
         v("limit", limit), v("count", count), v("held", held), v("cache_len", cache_len, optional=True),
         v("done", done), v("drafted", drafted, optional=True), v("accepted", accepted, optional=True),
         v("steps", steps, optional=True), tokens.data_ptr(), S, ts, history.data_ptr(), hs,
-        v("scratch", scratch, B * n), st), "mt_spec_accept")
+        v("scratch", scratch, B * n), st), "mt_spec_accept_p")
     return scratch
 
 

@@ -639,11 +639,12 @@ class HipKernelOps(TensorOps):
 
     @staticmethod
     def select_token(logits: Tensor, temperature: float = 0.0, top_k: int = 0, seed: int = 0, rows=None, **kw):
-        """The next token ids chosen on the device (mt_select_token) from logits [B, V], or from
+        """The next token ids chosen on the device (mt_select_token_p) from logits [B, V], or from
         one position of logits [B, T, V]: the last (read in place, no copy), or position rows[b]
         of batch row b (a prefill of right-padded prompts; the B rows are gathered first).
-        Returns (ids fp32 [B], ids int32 [B]) as torch device tensors; the keywords (seed_dev,
-        eos_id, out, out_i32, done, history, step_dev: torch device tensors) are _hip.select_token's."""
+        Returns (ids fp32 [B], ids int32 [B]) as torch device tensors; the keywords (top_p, min_p,
+        seed_dev, eos_id, out, out_i32, done, history, step_dev: torch device tensors) are
+        _hip.select_token's."""
         import torch
         v = _torch_view(logits)
         if v.dim() == 3:
@@ -665,8 +666,8 @@ class HipKernelOps(TensorOps):
     def spec_accept(logits, feed_i32, n_draft, limit, count, held, done, tokens, history, **kw):
         """Verify a speculative step's drafts against logits [B, k + 1, V] (a minitorch Tensor, or
         [B (k + 1), V] with k + 1 taken from feed_i32, or a torch view) and advance the row state in
-        place (mt_spec_accept). The keywords (scratch, cache_len, drafted, accepted, steps,
-        temperature, top_k, seed, seed_dev, eos_id) are _hip.spec_accept's."""
+        place (mt_spec_accept_p). The keywords (scratch, cache_len, drafted, accepted, steps,
+        temperature, top_k, top_p, min_p, seed, seed_dev, eos_id) are _hip.spec_accept's."""
         v = _torch_view(logits) if isinstance(logits, Tensor) else logits
         if v.dim() == 2:
             v = v.view(feed_i32.shape[0], -1, v.shape[1])

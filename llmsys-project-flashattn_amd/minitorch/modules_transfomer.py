@@ -370,7 +370,7 @@ class DecoderLM(Module):
     """Decoder-only pre-LN LM with 4 TransformerLayers (reference :365-470)."""
 
     # generate(graph=True) keeps device memory on the model: per batch size one KVCache and
-    # up to MAX_DECODE_GRAPHS captured steps (one per temperature / top_k / eos_id), for the
+    # up to MAX_DECODE_GRAPHS captured steps (one per temperature / top_k / eos_id / top_p / min_p), for the
     # MAX_DECODE_BATCH_SIZES most recently used batch sizes; drop_decode_graphs() frees it all
     MAX_DECODE_GRAPHS = 4
     MAX_DECODE_BATCH_SIZES = 4
@@ -541,7 +541,8 @@ class DecoderLM(Module):
 
     def generate(self, prompts, max_new_tokens: int, eos_id=None, use_cache: bool = True,
                  temperature: float = 0.0, top_k: int = 0, seed=None, graph: bool = False, sync_every: int = 8,
-                 prefill_chunk=None, kv_dtype=None, page_size=None, speculate=None, ngram: int = 3):
+                 prefill_chunk=None, kv_dtype=None, page_size=None, speculate=None, ngram: int = 3,
+                 top_p=None, min_p=None):
         """Decoding of a list of token-id lists, as the reference's generate
         (project/run_machine_translation.py:271-328); returns the new ids per prompt (without
         the eos that stopped a row). A row also stops once it holds more than n_positions tokens.
@@ -557,6 +558,15 @@ class DecoderLM(Module):
         with seed + t and the uniform draw of batch row b (use_cache=False runs every prompt as
         row 0 of its own batch, so its draws differ from the batched legs'). seed=None takes one
         seed from NumPy's global generator (np.random.seed reproduces a run, as for dropout).
+
+        top_p (in (0, 1]; None or 1: off) and min_p (in [0, 1]; None or 0: off) cut the sampled set
+        further, in the usual order after temperature and top_k (mt_select_token_p): top_p keeps
+        the most probable tokens up to a total probability of top_p (the nucleus; ties at its edge
+        enter by index, the most probable token always stays), min_p those of at least min_p
+        times the largest probability; the draw is from what both keep, renormalised. Greedy
+        decoding ignores them, as it ignores top_k. Every path chooses by the same kernel, so the
+        ids of a call do not depend on graph, speculate or the cache kind; a captured graph holds
+        both by value, beside temperature and top_k. Unset, nothing changes.
 
         graph=True (needs use_cache=True and the select_token kernel): the prompt is prefilled
         and the first token chosen eagerly; every further token is one replay of a captured
@@ -613,6 +623,12 @@ class DecoderLM(Module):
         temperature = float(temperature)
         if not temperature >= 0.0:
             raise ValueError(f"temperature must be >= 0, got {temperature}")
+        top_p = 1.0 if top_p is None else float(top_p)
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError(f"top_p must be None or in (0, 1], got {top_p}")
+        min_p = 0.0 if min_p is None else float(min_p)
+        if not 0.0 <= min_p <= 1.0:
+            raise ValueError(f"min_p must be None or in [0, 1], got {min_p}")
         if kv_dtype == "fp32":
             kv_dtype = None
         if kv_dtype is not None:
@@ -658,7 +674,7 @@ class DecoderLM(Module):
                 seed = 0  # greedy: never read, and NumPy's generator is left where it was
             elif seed is None:
                 seed = int(np.random.randint(0, 2**63 - 1, dtype=np.int64))
-            sampler = (temperature, int(top_k), int(seed))
+            sampler = (temperature, int(top_k), int(seed), top_p, min_p)
         was_training = self.training
         self.eval()
         try:
@@ -686,8 +702,8 @@ class DecoderLM(Module):
                 logits = self.forward(idx).to_numpy()
                 nxt = int(np.argmax(logits[0, len(tokens) - 1]))
             else:
-                nxt = int(self.backend.select_token(self.forward(idx), sampler[0], sampler[1],
-                                                    sampler[2] + len(new))[1].cpu().numpy()[0])
+                nxt = int(self.backend.select_token(self.forward(idx), sampler[0], sampler[1], sampler[2] + len(new),
+                                                    top_p=sampler[3], min_p=sampler[4])[1].cpu().numpy()[0])
             if eos_id is not None and nxt == eos_id:
                 break
             tokens.append(nxt)
@@ -732,8 +748,8 @@ class DecoderLM(Module):
             if sampler is None:
                 host = logits.to_numpy()
                 return np.argmax(host[np.arange(B), rows] if rows is not None else host[:, 0], axis=-1)
-            return self.backend.select_token(logits, sampler[0], sampler[1], sampler[2] + t,
-                                             rows=rows)[1].cpu().numpy()
+            return self.backend.select_token(logits, sampler[0], sampler[1], sampler[2] + t, rows=rows,
+                                             top_p=sampler[3], min_p=sampler[4])[1].cpu().numpy()
         nxt = choose(*self._prefill_logits(idx, lens, cache, prefill_chunk), 0)
         t = 0
         while True:
@@ -782,7 +798,7 @@ class DecoderLM(Module):
         cache.advance(1)
         self.backend.select_token(logits, st.temperature, st.top_k, seed_dev=st.seed, eos_id=st.eos_id,
                                   out=st.ids_dev, out_i32=st.ids_i32, done=st.done, history=st.history,
-                                  step_dev=st.step)
+                                  step_dev=st.step, top_p=st.top_p, min_p=st.min_p)
         st.step.add_(1)
         st.seed.add_(1)
 
@@ -801,7 +817,7 @@ class DecoderLM(Module):
         new = [[] for _ in range(B)]
         if max_new_tokens <= 0:
             return new
-        temperature, top_k, seed = sampler
+        temperature, top_k, seed, top_p, min_p = sampler
         graphs = self.__dict__.setdefault("_decode_graphs", {})
         slot = B if kv_dtype is None else (B, kv_dtype)  # a quantised cache has buffers and graphs of its own
         if page_size is not None:
@@ -818,7 +834,7 @@ class DecoderLM(Module):
                      "graphs": {}}
         graphs[slot] = entry  # most recently used last
         st = entry["state"]
-        st.begin(temperature, top_k, eos_id, seed)
+        st.begin(temperature, top_k, eos_id, seed, top_p, min_p)
         if page_size is not None:
             st.cache.reserve(final)  # the table is final before the first step: nothing changes while a graph replays
         # eager: the prefill (the prompt length varies) and the first token
@@ -829,7 +845,7 @@ class DecoderLM(Module):
         logits, rows = self._prefill_logits(idx, lens, st.cache, prefill_chunk)
         self.backend.select_token(logits, temperature, top_k, rows=rows, seed_dev=st.seed, eos_id=st.eos_id,
                                   out=st.ids_dev, out_i32=st.ids_i32, done=st.done, history=st.history,
-                                  step_dev=st.step)
+                                  step_dev=st.step, top_p=top_p, min_p=min_p)
         st.step.add_(1)
         st.seed.add_(1)
         # tokens row b can still return: max_new_tokens, or until it holds more than n_positions
@@ -840,7 +856,7 @@ class DecoderLM(Module):
         if total > 1:
             # the captured launches hold the sampling arguments by value (one graph per set of
             # them, the last MAX_DECODE_GRAPHS kept) and the parameters by address
-            args = (temperature, top_k, st.eos_id)
+            args = (temperature, top_k, st.eos_id, top_p, min_p)
             params = tuple(p.value._tensor.data_ptr() for p in self.parameters())
             held = entry["graphs"].pop(args, None)
             if held is not None and held[1] == params:
@@ -911,7 +927,7 @@ class DecoderLM(Module):
         self.backend.spec_accept(logits, st.feed_i32, st.n_draft, st.limit, st.count, st.held, st.done, st.tokens,
                                  st.history, scratch=st.scratch, cache_len=cache.length, drafted=st.drafted,
                                  accepted=st.accepted, steps=st.steps, temperature=st.temperature, top_k=st.top_k,
-                                 seed_dev=st.seed, eos_id=st.eos_id)
+                                 top_p=st.top_p, min_p=st.min_p, seed_dev=st.seed, eos_id=st.eos_id)
 
     def _generate_spec(self, prompts, max_new_tokens, eos_id, sampler, sync_every, prefill_chunk, kv_dtype,
                        page_size, k, ngram, graph):
@@ -925,7 +941,7 @@ class DecoderLM(Module):
         self.spec_stats = dict(steps=0, tokens=0, drafted=0, accepted=0)
         if max_new_tokens <= 0:
             return new
-        temperature, top_k, seed = sampler
+        temperature, top_k, seed, top_p, min_p = sampler
         final = n_pages = None
         if page_size is not None:
             # the k + 1 rows a step appends are reserved up front too, a finished row's included, so
@@ -946,7 +962,7 @@ class DecoderLM(Module):
             st = entry["state"]
         else:
             st = _SpecState(self, B, k, kv_dtype, page_size, n_pages)
-        st.begin(temperature, top_k, eos_id, seed)
+        st.begin(temperature, top_k, eos_id, seed, top_p, min_p)
         if page_size is not None:
             st.cache.reserve(final)
         # eager, as without speculation: the prefill and the first token (token number 0: the base seed)
@@ -957,7 +973,7 @@ class DecoderLM(Module):
         logits, rows = self._prefill_logits(idx, lens, st.cache, prefill_chunk)
         self.backend.select_token(logits, temperature, top_k, rows=rows, seed_dev=st.seed, eos_id=st.eos_id,
                                   out=st.ids_dev, out_i32=st.ids_i32, done=st.done, history=st.history,
-                                  step_dev=st.step)
+                                  step_dev=st.step, top_p=top_p, min_p=min_p)
         # tokens row b can still return: max_new_tokens, or until it holds more than n_positions
         limit = np.minimum(max_new_tokens, self.n_positions - lens + 1)
         st.start(idx, lens, limit)
@@ -971,7 +987,7 @@ class DecoderLM(Module):
             me = weakref.ref(self)  # no model <-> step-function cycle (see _generate_graph)
             step = lambda: me()._spec_step(st, ngram)  # noqa: E731
             if graph:
-                args = (temperature, top_k, st.eos_id, k, ngram)
+                args = (temperature, top_k, st.eos_id, k, ngram, top_p, min_p)
                 params = tuple(p.value._tensor.data_ptr() for p in self.parameters())
                 held = entry["graphs"].pop(args, None)
                 if held is not None and held[1] == params:
@@ -1026,10 +1042,12 @@ class _DecodeState:
         self.step = torch.zeros(1, dtype=torch.int32, device="cuda")
         self.seed = torch.zeros(1, dtype=torch.int64, device="cuda")
         self.temperature, self.top_k, self.eos_id = 0.0, 0, None
+        self.top_p, self.min_p = 1.0, 0.0
 
-    def begin(self, temperature, top_k, eos_id, seed: int) -> None:
+    def begin(self, temperature, top_k, eos_id, seed: int, top_p: float = 1.0, min_p: float = 0.0) -> None:
         """A new call: an empty cache, no row done, step 0, the call's seed."""
         self.temperature, self.top_k = temperature, top_k
+        self.top_p, self.min_p = top_p, min_p
         self.eos_id = None if eos_id is None else int(eos_id)
         self.cache.reset()
         self.done.zero_()

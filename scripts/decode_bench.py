@@ -24,7 +24,10 @@ End to end: DecoderLM.generate tokens/s at config-5 width (V = 10000, E = 256, 8
                 greedy, and one sampled graph leg (T = 0.8, top_k = 50); host clock around calls
                 that end in a device-to-host copy; the legs alternate inside every round
   select_token  mt_select_token alone at (B, V) = (8, 10000) and (64, 10000): greedy, top_k = 50
-                and the whole vocabulary at T = 1, device events around 64 launches, alternated
+                and the whole vocabulary at T = 1, and the nucleus legs top_p = 0.9 over the whole
+                vocabulary, top_k = 50 with top_p = 0.9, and min_p = 0.05 (mt_select_token_p; left
+                out with a --lib build that predates it); device events around 64 launches,
+                alternated
 
 --gqa-legs instead writes profiles/decode_gqa_bench.json: per large shape and Hkv in {H, H/4, H/8},
 alternated in one process like the legs above:
@@ -821,6 +824,10 @@ def bench_select(torch, _hip, B, V, rounds, warmup, inner=64):
     out_i = torch.empty(B, dtype=torch.int32, device="cuda")
     kinds = {"greedy": dict(temperature=0.0), "top_k_50": dict(temperature=1.0, top_k=50),
              "whole_vocabulary": dict(temperature=1.0, top_k=0)}
+    if hasattr(_hip.lib(), "mt_select_token_p"):  # an older build under --lib runs the three legs above
+        kinds.update({"top_p_0.9": dict(temperature=1.0, top_k=0, top_p=0.9),
+                      "top_k_50_top_p_0.9": dict(temperature=1.0, top_k=50, top_p=0.9),
+                      "min_p_0.05": dict(temperature=1.0, top_k=0, min_p=0.05)})
     legs = {k: (lambda i, kw=kw: _hip.select_token(logits, seed=i, out=out, out_i32=out_i, **kw)) for k, kw in kinds.items()}
     for fn in legs.values():
         for _ in range(warmup):
