@@ -510,6 +510,34 @@ int mt_rope(int dtype, int inverse,
             int64_t B, int64_t T, int64_t d, const float* cos, const float* sin, int64_t n_pos,
             const int* pos0, void* stream);
 
+/* ---- fused skinny linear (the cached decode step's projections) -------------
+ * For g < G groups that share x (Q, K and V in one launch), fp32:
+ *   xh    = prologue(x)                     x [M, K], rows contiguous, ldx elements apart
+ *   out_g = epilogue_g(xh @ W_g)            W_g [K, N_g] and out_g [M, N_g] row-major contiguous
+ * prologue: gamma / beta NULL: none; else LayerNorm over K with mt_layernorm_fw's formula
+ *   (mu = E[x], var = E[x^2] - mu^2 + 1e-8, xh = gamma (x - mu) / sqrt(var) + beta).
+ * epilogue_g, each stage present when its operand is: + bias[g] [N_g], then GELU_tanh
+ *   (mt_bias_gelu_fw's formula) when bit g of gelu_mask is set, then + residual[g] [M, N_g]
+ *   (contiguous). bias / residual: NULL for none in any group, or arrays of G pointers (NULL
+ *   entries allowed).
+ * Range: 1 <= G <= 3, 1 <= M <= 64, K a multiple of 4 in 4..1024, 1 <= N_g < 2^31 - 64 (any
+ * value, 1 and 10000 included). x, gamma and beta 16-byte aligned, ldx a multiple of 4 and >= K;
+ * the other pointers 4-byte aligned (with N_g % 4 == 0 and 16-byte alignment they move 16 bytes
+ * per access; the values do not depend on that).
+ * One launch, a workgroup per 64 output columns of a group holding all M rows; every element of
+ * W is read once; products on the fp32 MFMA, no atomics. The bits of out row m are a function of
+ * x row m, residual row m, the weights and (K, N_g) alone: not of M, of m, of G or of the stages
+ * that are on (a one-row call and row m of a 64-row call agree bit for bit). Allocates nothing,
+ * does not synchronise, stream-ordered (capturable).
+ * Refused with a status and a mt_last_error() message before any device call: G, M, K, ldx or
+ * an N_g out of range; x, W, N, out, a W_g or an out_g NULL; gamma without beta or the reverse;
+ * a misaligned pointer; gelu_mask naming a group >= G; an out_g that overlaps x, a residual or
+ * another out. */
+int mt_linear_rows(int G, const float* x, int64_t ldx, int64_t M, int64_t K, const float* gamma,
+                   const float* beta, const float* const* W, const int64_t* N,
+                   const float* const* bias, const float* const* residual, float* const* out,
+                   int gelu_mask, void* stream);
+
 /* ---- FlashAttention, reference-compatible host pointers (fp32) ------------ */
 /* reference src/flashattention_kernel.cu:259 */
 void launch_flashattention_forward(float* Q, float* K, float* V, float* O, float* l, float* m,

@@ -104,6 +104,7 @@ _PROTOS = {
                               _vp]),
     "mt_rope": (_int, [_int, _int, _vp, _vp, _i64, _i64p, _i64p, _vp, _vp, _i64, _i64p, _i64p,
                        _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "mt_linear_rows": (_int, [_int, _vp, _i64, _i64, _i64, _vp, _vp, _vpp, _i64p, _vpp, _vpp, _vpp, _int, _vp]),
     "mt_attn_softmax_fw": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64p, _int, _vp]),
     "mt_attn_softmax_bw": (_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "mt_layernorm_fw": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
@@ -1062,6 +1063,60 @@ def rope(x, cos, sin, pos0=None, inverse: bool = False, out=None, x2=None, out2=
         B, T, d, cos.data_ptr(), sin.data_ptr(), cos.shape[0], None if p is None else p.data_ptr(), st),
         "mt_rope")
     return out if x2 is None else (out, out2)
+
+
+fused_linear_calls = 0  # launches of mt_linear_rows through fused_linear (tests tell the path by it)
+
+
+def fused_linear(x, weights, biases=None, residuals=None, gamma=None, beta=None, gelu=False, outs=None,
+                 stream: Optional[int] = None):
+    """The fused skinny linear (mt_linear_rows; fp32): out_g = epilogue_g(prologue(x) @ W_g) for the
+    1..3 weights W_g [K, N_g] (dense) over the shared x [M <= 64, K] (unit-stride rows), one launch.
+    gamma / beta [K]: LayerNorm x first (both or neither). biases / residuals: None, or one entry
+    per weight ([N_g] / dense [M, N_g]; None entries skip the stage). gelu: a bool for all groups
+    or one per group (GELU_tanh after the bias). outs: dense [M, N_g] tensors to write into
+    (allocated when None). Returns the list of outputs. Inference only."""
+    global fused_linear_calls
+    torch = _torch()
+    G = len(weights)
+    _check_dev(x, *weights)
+    if x.dim() != 2 or x.dtype != torch.float32 or (x.stride(1) != 1 and x.shape[1] != 1):
+        raise ValueError(f"fused_linear takes a float32 [M, K] x with unit-stride rows, got {tuple(x.shape)} {x.dtype}")
+    M, K = x.shape
+    for name, group in (("biases", biases), ("residuals", residuals), ("outs", outs)):
+        if group is not None and len(group) != G:
+            raise ValueError(f"fused_linear: {name} has {len(group)} entries for {G} weights")
+    if (gamma is None) != (beta is None):
+        raise ValueError("fused_linear: gamma and beta go together")
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != K or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError(f"fused_linear: {name} must be a dense device float32 [{K}] tensor")
+    gelu = [bool(gelu)] * G if isinstance(gelu, (bool, int)) else [bool(v) for v in gelu]
+    if len(gelu) != G:
+        raise ValueError(f"fused_linear: gelu has {len(gelu)} entries for {G} weights")
+    biases = [None] * G if biases is None else list(biases)
+    residuals = [None] * G if residuals is None else list(residuals)
+    outs = [None] * G if outs is None else list(outs)
+    for g, w in enumerate(weights):
+        if w.dim() != 2 or w.shape[0] != K or w.dtype != torch.float32 or not w.is_contiguous():
+            raise ValueError(f"fused_linear: weight {g} must be a dense float32 [{K}, N] tensor, got {tuple(w.shape)}")
+        n = w.shape[1]
+        for name, t, shape in (("bias", biases[g], (n,)), ("residual", residuals[g], (M, n)), ("out", outs[g], (M, n))):
+            if t is None:
+                continue
+            if t.dtype != torch.float32 or t.numel() != (n if len(shape) == 1 else M * n) or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"fused_linear: {name} {g} must be a dense device float32 {list(shape)} tensor")
+        if outs[g] is None:
+            outs[g] = torch.empty((M, n), dtype=torch.float32, device=x.device)
+    ptrs = lambda ts: (ctypes.c_void_p * G)(*[None if t is None else t.data_ptr() for t in ts])  # noqa: E731
+    mask = sum(1 << g for g in range(G) if gelu[g])
+    st = stream_ptr(x.device) if stream is None else stream
+    check(lib().mt_linear_rows(
+        G, x.data_ptr(), x.stride(0) if M > 1 else K, M, K, None if gamma is None else gamma.data_ptr(),
+        None if beta is None else beta.data_ptr(), ptrs(weights), (ctypes.c_int64 * G)(*[w.shape[1] for w in weights]),
+        ptrs(biases), ptrs(residuals), ptrs(outs), mask, st), "mt_linear_rows")
+    fused_linear_calls += 1
+    return outs
 
 
 def scratch_bytes() -> int:

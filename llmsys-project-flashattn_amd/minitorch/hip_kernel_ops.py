@@ -701,3 +701,19 @@ class HipKernelOps(TensorOps):
                   pos0=None if pos0 is None else HipKernelOps._i32(pos0), inverse=inverse, out=outs[0],
                   x2=None if x2 is None else views[1], out2=None if x2 is None else outs[1])
         return res[0] if x2 is None else (res[0], res[1])
+
+    @staticmethod
+    def fused_linear(x: Tensor, weights, biases=None, residuals=None, ln=None, gelu=False):
+        """The fused skinny linear of a cached decode step (mt_linear_rows): for the 1..3 dense
+        weights W_g [K, N_g] over the shared x [M <= 64, K], out_g = (+ residual_g)(GELU)(+ bias_g)
+        (LayerNorm(x) @ W_g) in one launch. ln: (gamma, beta) to normalise x first, or None;
+        biases / residuals: None or one entry per weight (None entries skip the stage); gelu: one
+        bool, or one per weight. Returns the list of new [M, N_g] tensors (no history: inference
+        only)."""
+        dense = lambda t: None if t is None else _torch_view(_dense(t))  # noqa: E731
+        group = lambda ts: None if ts is None else [dense(t) for t in ts]  # noqa: E731
+        xv = _torch_view(x if x._tensor.strides[-1] == 1 else x.contiguous())
+        outs = _hip.fused_linear(xv, [dense(w) for w in weights], group(biases), group(residuals),
+                                 gamma=None if ln is None else dense(ln[0]).reshape(-1),
+                                 beta=None if ln is None else dense(ln[1]).reshape(-1), gelu=gelu)
+        return [_wrap(o.reshape(-1), o.shape, x.backend) for o in outs]

@@ -80,11 +80,29 @@ def _group_ones(group: int, backend):
 
 datatype = np.float32
 
+# rows (batch x tokens) and input width the fused skinny linear takes (mt_linear_rows)
+FUSED_STEP_MAX_ROWS = 64
+FUSED_STEP_MAX_WIDTH = 1024
+
+
+def _bias(linear):
+    return None if linear.bias is None else linear.bias.value
+
+
+def _takes_fused_step(module, rows: int, width: int, backend, p_dropout: float) -> bool:
+    """Whether a cached step of `rows` rows runs on the fused skinny linear: the module was built
+    with fused_step=True, no dropout is live, the rows and the width are in the kernel's range
+    and the backend has it. Decided per call from the shapes; everything else takes the
+    unfused path."""
+    return (bool(module.fused_step) and not (module.training and p_dropout > 0)
+            and rows <= FUSED_STEP_MAX_ROWS and width % 4 == 0 and width <= FUSED_STEP_MAX_WIDTH
+            and getattr(backend, "fused_linear", None) is not None)
+
 
 class MultiHeadAttention(Module):
     def __init__(self, n_embd: int, n_head: int, causal: bool = False, p_dropout: float = 0.1,
                  bias: bool = True, backend=None, use_fused_kernel: bool = False,
-                 use_flash_attention: bool = False, n_kv_head=None, rope=None):
+                 use_flash_attention: bool = False, n_kv_head=None, rope=None, fused_step: bool = False):
         """n_kv_head: grouped-query attention. The n_head query heads share n_kv_head key / value
         heads in groups of n_head // n_kv_head (query head h uses kv head h // group; 1 is
         multi-query attention). None: n_head, every head its own K and V.
@@ -92,8 +110,11 @@ class MultiHeadAttention(Module):
         tokens' positions right after the projection, so every attention branch and the KV cache
         see rotated tensors: by the rope kernel when use_fused_kernel is set and the backend has
         it, by the tensor-op form otherwise (rotary.apply_rope). With a cache the rotation is
-        always the kernel's, one launch for Q and K, in place, at the cache's device lengths."""
+        always the kernel's, one launch for Q and K, in place, at the cache's device lengths.
+        fused_step: a cached step of at most 64 rows may be run by forward_fused (the caller,
+        TransformerLayer, decides per call); forward itself never changes."""
         super().__init__()
+        self.fused_step = bool(fused_step)
         if n_kv_head is None:
             n_kv_head = n_head
         if n_kv_head <= 0 or n_head % n_kv_head:
@@ -208,6 +229,23 @@ class MultiHeadAttention(Module):
             attn = self._cached_attention(q, k, v, kv_len, cache)
         return self.out_projection(attn.view(batch_size * seq_len, n_embd)).view(batch_size, seq_len, n_embd)
 
+    def forward_fused(self, flat, batch_size: int, seq_len: int, kv_len, cache, ln):
+        """forward for a decode or extend step on the fused skinny linear: flat [B T, n_embd] is
+        the block's un-normalised input. One launch normalises it (ln: the block's FusedLayerNorm)
+        and projects Q, K and V with their biases; rope, the cache append and the attention are
+        forward's; the output projection adds its bias and flat (the residual) in its epilogue.
+        Returns [B T, n_embd]: attention(ln(flat)) + flat."""
+        proj = (self.q_projection, self.k_projection, self.v_projection)
+        biases = [_bias(p) for p in proj]
+        q, k, v = flat.fused_linear([p.weights.value for p in proj], None if biases[0] is None else biases,
+                                    ln=(ln.gamma, ln.beta))
+        shp = (batch_size, seq_len, self.n_head, self.attn_hidden_dim)
+        kv_shp = (batch_size, seq_len, self.n_kv_head, self.attn_hidden_dim)
+        q, k, v = q.view(*shp).permute(0, 2, 1, 3), k.view(*kv_shp).permute(0, 2, 1, 3), v.view(*kv_shp).permute(0, 2, 1, 3)
+        attn = self._cached_attention(q, k, v, kv_len, cache)
+        return attn.view(batch_size * seq_len, self.n_embd).fused_linear(
+            self.out_projection.weights.value, _bias(self.out_projection), residual=flat)
+
     def _cached_attention(self, q, k, v, kv_len, cache):
         from .kv_cache import KVCache
         if not self.use_flash_attention:
@@ -317,8 +355,9 @@ class MultiHeadAttention(Module):
 
 class FeedForward(Module):
     def __init__(self, n_embd: int, middle_dim: int = 256, p_dropout: float = 0.1, bias: bool = True,
-                 backend=None):
+                 backend=None, fused_step: bool = False):
         super().__init__()
+        self.fused_step = bool(fused_step)
         self.linear_in = Linear(n_embd, middle_dim, bias=bias, backend=backend)
         self.linear_out = Linear(middle_dim, n_embd, bias=bias, backend=backend)
         self.dropout = Dropout(p_dropout)
@@ -337,19 +376,38 @@ class FeedForward(Module):
         return self.dropout(self.linear_out(h)).view(batch_size, seq_len, n_embd)
 
 
+    def forward_fused(self, flat, ln):
+        """forward for a cached step on the fused skinny linear: flat [rows, n_embd] is the
+        un-normalised input; linear_in takes ln (the block's FusedLayerNorm), its bias and the
+        GELU in one launch, linear_out its bias and the residual flat in another. Returns
+        [rows, n_embd]: ff(ln(flat)) + flat (no dropout: the caller checked)."""
+        h = flat.fused_linear(self.linear_in.weights.value, _bias(self.linear_in), ln=(ln.gamma, ln.beta), gelu=True)
+        return h.fused_linear(self.linear_out.weights.value, _bias(self.linear_out), residual=flat)
+
+
 class TransformerLayer(Module):
     """Pre-LN transformer block (reference :279-362)."""
 
     def __init__(self, n_embd: int, n_head: int, p_dropout: float = 0.1, ln_eps: float = 1e-8,
                  bias: bool = True, backend=None, use_fused_kernel: bool = False,
-                 use_flash_attention: bool = False, causal: bool = True, n_kv_head=None, rope=None):
+                 use_flash_attention: bool = False, causal: bool = True, n_kv_head=None, rope=None,
+                 fused_step: bool = False):
+        """fused_step (needs use_fused_kernel=True: the layer norms must be FusedLayerNorm): a
+        decode or extend step of at most 64 rows on a filled cache runs on the fused skinny linear
+        (_forward_fused); the prefill, larger steps, live dropout and a call without a cache take
+        the unfused path. Unset, nothing changes."""
         super().__init__()
+        if fused_step and not use_fused_kernel:
+            raise ValueError("fused_step=True needs use_fused_kernel=True (the fused step reads FusedLayerNorm's "
+                             "parameters)")
+        self.fused_step = bool(fused_step)
+        self.p_dropout = p_dropout
         self.attention = MultiHeadAttention(n_embd, n_head, causal=causal, p_dropout=p_dropout,
                                             bias=bias, backend=backend,
                                             use_fused_kernel=use_fused_kernel,
                                             use_flash_attention=use_flash_attention, n_kv_head=n_kv_head,
-                                            rope=rope)
-        self.ff = FeedForward(n_embd, 256, p_dropout, bias, backend)
+                                            rope=rope, fused_step=fused_step)
+        self.ff = FeedForward(n_embd, 256, p_dropout, bias, backend, fused_step=fused_step)
         self.use_fused_kernel = use_fused_kernel
         if use_fused_kernel:
             self.ln_1 = FusedLayerNorm(n_embd, backend)
@@ -360,10 +418,23 @@ class TransformerLayer(Module):
 
     def forward(self, x, kv_len=None, cache=None):
         batch_size, seq_len, x_dim = x.shape
+        if cache is not None and _takes_fused_step(self, batch_size * seq_len, x_dim, x.backend, self.p_dropout):
+            lkv = cache.layer(0) if hasattr(cache, "layer") else cache  # a one-layer KVCache: its layer 0
+            if not lkv.cache.empty:  # the prefill takes the unfused path
+                return self._forward_fused(x, kv_len, lkv)
         a = self.ln_1(x.view(batch_size * seq_len, x_dim)).view(batch_size, seq_len, x_dim)
         a = (self.attention(a, kv_len) if cache is None else self.attention(a, kv_len, cache)) + x
         h = self.ln_2(a.view(batch_size * seq_len, x_dim)).view(batch_size, seq_len, x_dim)
         return self.ff(h) + a
+
+    def _forward_fused(self, x, kv_len, cache):
+        """The block of a cached step in five launches beside the attention's own: ln_1 + Q / K / V
+        (+ biases), [rope, append, attention], out_projection + bias + x, ln_2 + linear_in + bias
+        + GELU, linear_out + bias + residual. cache: this layer's LayerKV, filled."""
+        batch_size, seq_len, x_dim = x.shape
+        flat = x.contiguous().view(batch_size * seq_len, x_dim)
+        a = self.attention.forward_fused(flat, batch_size, seq_len, kv_len, cache, self.ln_1)
+        return self.ff.forward_fused(a, self.ln_2).view(batch_size, seq_len, x_dim)
 
 
 class DecoderLM(Module):
@@ -378,14 +449,29 @@ class DecoderLM(Module):
     def __init__(self, n_vocab: int, n_embd: int, n_head: int, n_positions: int,
                  p_dropout: float = 0.1, ln_eps: float = 1e-5, bias: bool = True, backend=None,
                  use_fused_kernel: bool = False, use_flash_attention: bool = False, n_layer: int = 4,
-                 n_kv_head=None, pos_encoding: str = "learned", rope_theta: float = 10000.0):
-        """pos_encoding: "learned" adds a learned position_embeddings row to every token's
+                 n_kv_head=None, pos_encoding: str = "learned", rope_theta: float = 10000.0,
+                 fused_step: bool = False):
+        """fused_step (needs use_fused_kernel=True; fixed at construction): every decode or extend
+        step of at most 64 rows (batch x tokens) on a filled KV cache runs its linears on the fused
+        skinny linear (Tensor.fused_linear, mt_linear_rows): per layer ln_1 + Q / K / V in one
+        launch, the output projection with its bias and residual in one, ln_2 + linear_in + GELU in
+        one, linear_out + bias + residual in one; the final ln and lm_head in one. The prefill,
+        larger steps, training with live dropout and calls without a cache take the unfused
+        path, chosen per call from the shapes. The kernel's rows do not depend on the rows beside
+        them, so generate returns the same ids eager, with graph=True and with speculate. Unset,
+        nothing changes.
+        pos_encoding: "learned" adds a learned position_embeddings row to every token's
         embedding (the reference's model); "rope" has no position parameter: one RotaryTable
         (n_positions rows, base rope_theta), shared by all layers, rotates every layer's Q and K
         (MultiHeadAttention(rope=...)) and the token embeddings are fed alone."""
         super().__init__()
         if pos_encoding not in ("learned", "rope"):
             raise ValueError(f'pos_encoding must be "learned" or "rope", got {pos_encoding!r}')
+        if fused_step and not use_fused_kernel:
+            raise ValueError("fused_step=True needs use_fused_kernel=True (the fused step reads FusedLayerNorm's "
+                             "parameters)")
+        self.fused_step = bool(fused_step)
+        self.p_dropout = p_dropout
         self.backend = backend
         self.n_embd = n_embd
         self.n_vocab = n_vocab
@@ -401,7 +487,7 @@ class DecoderLM(Module):
             setattr(self, f"t_layer_{i + 1}", TransformerLayer(
                 n_embd, n_head, p_dropout, ln_eps, bias, backend,
                 use_fused_kernel=use_fused_kernel, use_flash_attention=use_flash_attention,
-                n_kv_head=n_kv_head, rope=self.rope))
+                n_kv_head=n_kv_head, rope=self.rope, fused_step=fused_step))
         self.dropout = Dropout(p_dropout)
         self.lm_head = Linear(n_embd, n_vocab, bias, backend)
         self.use_fused_kernel = use_fused_kernel
@@ -436,6 +522,13 @@ class DecoderLM(Module):
             h = getattr(self, f"t_layer_{i + 1}")(h, kv_len)
         h = self.ln(h.view(batch_size * seq_len, self.n_embd))
         return self.lm_head(h).view(batch_size, seq_len, self.n_vocab)
+
+    def _head(self, flat, step: bool = False):
+        """The final LayerNorm and lm_head over flat [rows, n_embd]; for a decode or extend step
+        (step=True) of a fused_step model within the fused kernel's range, one launch."""
+        if step and _takes_fused_step(self, flat.shape[0], self.n_embd, flat.backend, self.p_dropout):
+            return flat.fused_linear(self.lm_head.weights.value, _bias(self.lm_head), ln=(self.ln.gamma, self.ln.beta))
+        return self.lm_head(self.ln(flat))
 
     def new_cache(self, batch_size: int, kv_dtype=None, page_size=None, n_pages=None):
         """A KVCache for this model and a batch of batch_size rows. kv_dtype: None / "fp32", or
@@ -475,8 +568,8 @@ class DecoderLM(Module):
         h = self.dropout(h)
         for i in range(self.n_layer):
             h = getattr(self, f"t_layer_{i + 1}")(h, kv_len, cache.layer(i))
-        h = self.ln(h.view(batch_size * seq_len, self.n_embd))
-        out = self.lm_head(h).view(batch_size, seq_len, self.n_vocab)
+        out = self._head(h.view(batch_size * seq_len, self.n_embd), step=not prefill)
+        out = out.view(batch_size, seq_len, self.n_vocab)
         if prefill and kv_len is not None:
             from .tensor import Tensor
             held = kv_len.to_numpy() if isinstance(kv_len, Tensor) else kv_len
@@ -507,8 +600,7 @@ class DecoderLM(Module):
         h = self.dropout(h)
         for i in range(self.n_layer):
             h = getattr(self, f"t_layer_{i + 1}")(h, new_len, cache.layer(i))
-        h = self.ln(h.view(batch_size * seq_len, self.n_embd))
-        out = self.lm_head(h).view(batch_size, seq_len, self.n_vocab)
+        out = self._head(h.view(batch_size * seq_len, self.n_embd), step=True).view(batch_size, seq_len, self.n_vocab)
         cache.advance(new_len)
         return out
 
@@ -793,8 +885,7 @@ class DecoderLM(Module):
         h = self.dropout(h)
         for i in range(self.n_layer):
             h = getattr(self, f"t_layer_{i + 1}")(h, None, cache.layer(i))
-        h = self.ln(h.view(B, self.n_embd))
-        logits = self.lm_head(h)
+        logits = self._head(h.view(B, self.n_embd), step=True)
         cache.advance(1)
         self.backend.select_token(logits, st.temperature, st.top_k, seed_dev=st.seed, eos_id=st.eos_id,
                                   out=st.ids_dev, out_i32=st.ids_i32, done=st.done, history=st.history,
@@ -922,8 +1013,7 @@ class DecoderLM(Module):
         h = self.dropout(h)
         for i in range(self.n_layer):
             h = getattr(self, f"t_layer_{i + 1}")(h, None, cache.layer(i))
-        h = self.ln(h.view(B * n, self.n_embd))
-        logits = self.lm_head(h).view(B, n, self.n_vocab)
+        logits = self._head(h.view(B * n, self.n_embd), step=True).view(B, n, self.n_vocab)
         self.backend.spec_accept(logits, st.feed_i32, st.n_draft, st.limit, st.count, st.held, st.done, st.tokens,
                                  st.history, scratch=st.scratch, cache_len=cache.length, drafted=st.drafted,
                                  accepted=st.accepted, steps=st.steps, temperature=st.temperature, top_k=st.top_k,

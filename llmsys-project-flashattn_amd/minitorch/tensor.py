@@ -372,6 +372,21 @@ class Tensor:
             raise NotImplementedError("this backend has no extend attention kernel")
         return fn(self, Kc, Vc, visible, q_len, causal)
 
+    def fused_linear(self, weight, bias=None, residual=None, ln=None, gelu=False):
+        """Generation: self [M <= 64, K] through one launch of the fused skinny linear,
+        (+ residual)(GELU_tanh)(+ bias)(LayerNorm(self) @ weight); ln: (gamma, beta) or None. weight
+        may be a list of 1..3 weights that share self (Q, K and V), bias / residual / gelu then
+        lists too (or None / one bool); the result is then a list. Inference only: the result has
+        no history, whatever the inputs' (as flash_attention_decode's), so nothing differentiates
+        through it; a backend without the kernel raises."""
+        fn = getattr(self.backend, "fused_linear", None)
+        if fn is None:
+            raise NotImplementedError("this backend has no fused skinny linear kernel (HipKernelOps has)")
+        if isinstance(weight, (list, tuple)):
+            return fn(self, list(weight), bias, residual, ln, gelu)
+        return fn(self, [weight], None if bias is None else [bias], None if residual is None else [residual],
+                  ln, gelu)[0]
+
     def rope(self, table, pos0=None) -> "Tensor":
         """Rotary position embedding of the head rows of self [B,H,T,d] by a RotaryTable: token t
         of batch row b is rotated to position min(max(pos0[b], 0) + t, n_positions - 1) (pos0: a

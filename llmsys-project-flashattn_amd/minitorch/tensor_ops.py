@@ -148,5 +148,8 @@ class TensorBackend:
         # generate(speculate=...) needs them)
         self.spec_draft = getattr(ops, "spec_draft", None)
         self.spec_accept = getattr(ops, "spec_accept", None)
+        # the fused skinny linear of a cached decode step (optional: DecoderLM(fused_step=True)
+        # needs it)
+        self.fused_linear = getattr(ops, "fused_linear", None)
         # rotary position embedding as one kernel (optional: a backend without it runs the tensor-op form)
         self.rope = getattr(ops, "rope", None)

@@ -1123,6 +1123,125 @@ def spec_legs(args, torch, minitorch, _hip):
         json.dump(res, f, indent=1)
 
 
+FUSED_SHAPES = [(1, 256, 256), (8, 256, 256), (64, 256, 256), (8, 256, 10000)]
+
+
+def bench_fused_kernel(torch, minitorch, _hip, M, K, N, rounds, warmup, inner=32):
+    """mt_linear_rows against what it replaces (mt_layernorm_fw -> mt_matmul_f32 -> the bias add
+    or mt_bias_gelu_fw -> the residual add, through the HIP backend's tensor ops) for the fusion
+    combinations the model uses; each leg is `inner` calls replayed from one captured graph, so
+    the host's launch path is out of both. Warm: the operands stay in cache between calls."""
+    from minitorch.tensor_functions import BiasGelu
+    hip = minitorch.TensorBackend(minitorch.HipKernelOps)
+    rng = np.random.default_rng(0)
+    t = lambda a: minitorch.tensor_from_numpy(np.ascontiguousarray(a, dtype=np.float32), hip)  # noqa: E731
+    x, res = t(rng.normal(0.5, 1, (M, K))), t(rng.standard_normal((M, N)))
+    gamma, beta = t(1 + 0.3 * rng.standard_normal(K)), t(0.2 * rng.standard_normal(K))
+    Ws = [t(rng.uniform(-K ** -0.5, K ** -0.5, (K, N))) for _ in range(3)]
+    bs = [t(rng.uniform(-K ** -0.5, K ** -0.5, N)) for _ in range(3)]
+    W, b = Ws[0], bs[0]
+    ln = (gamma, beta)
+
+    def unfused_qkv():
+        h = x.layernorm(gamma, beta)
+        return [h @ w + c for w, c in zip(Ws, bs)]
+    pairs = {
+        "ln_bias": (lambda: x.fused_linear(W, b, ln=ln), lambda: x.layernorm(gamma, beta) @ W + b),
+        "ln_bias_x3_grouped": (lambda: x.fused_linear(Ws, bs, ln=ln), unfused_qkv),
+        "bias_residual": (lambda: x.fused_linear(W, b, residual=res), lambda: (x @ W + b) + res),
+        "ln_bias_gelu": (lambda: x.fused_linear(W, b, ln=ln, gelu=True),
+                         lambda: BiasGelu.apply(x.layernorm(gamma, beta) @ W, b)),
+    }
+    legs = {}
+    for name, (fused, unfused) in pairs.items():
+        legs[f"{name}_fused"] = _graph_of(torch, lambda i, f=fused: f(), inner)
+        legs[f"{name}_unfused"] = _graph_of(torch, lambda i, f=unfused: f(), inner)
+    copy_src, copy_dst = torch.empty(K * N, device="cuda"), torch.empty(K * N, device="cuda")
+    legs["copy_of_W_bytes"] = _graph_of(torch, lambda i: copy_dst.copy_(copy_src), inner)
+    for fn in legs.values():
+        for _ in range(warmup):
+            _timed(torch, fn, 1)
+    times = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():  # alternated
+            times[k].append(_timed(torch, fn, 1) / inner)
+    out = {"M": M, "K": K, "N": N, "rounds": rounds, "calls_per_replay": inner, "W_bytes": 4 * K * N,
+           **{f"{k}_s_median": statistics.median(v) for k, v in times.items()},
+           **{f"{k}_s_min": min(v) for k, v in times.items()}}
+    for name in pairs:
+        out[f"{name}_unfused_over_fused"] = out[f"{name}_unfused_s_median"] / out[f"{name}_fused_s_median"]
+    return out
+
+
+def _graph_kernel_nodes(torch, lm):
+    """Kernel nodes of the model's captured decode-step graphs (newest entry): torch's debug dump
+    is not used; the count comes from replaying under the profiler."""
+    from torch.profiler import ProfilerActivity, profile
+    graphs = [g for e in lm._decode_graphs.values() for g, _ in e["graphs"].values()]
+    g = graphs[-1]
+    g.replay()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        g.replay()
+        torch.cuda.synchronize()
+    return sum(1 for ev in prof.events() if ev.device_type.name == "CUDA")
+
+
+def bench_generate_fused(torch, minitorch, n_positions, prompt_len, new_tokens, batch, rounds):
+    backend = minitorch.TensorBackend(minitorch.HipKernelOps)
+    rng = np.random.default_rng(0)
+    prompts = [[int(t) for t in rng.integers(0, 10000, prompt_len)] for _ in range(batch)]
+    sample = dict(temperature=0.8, top_k=50, seed=1)
+    lms = {}
+    for name, fused in (("unfused", False), ("fused", True)):
+        np.random.seed(0)  # the same weights
+        lms[name] = minitorch.DecoderLM(n_vocab=10000, n_embd=256, n_head=8, n_positions=n_positions, p_dropout=0.0,
+                                        backend=backend, use_fused_kernel=True, use_flash_attention=True,
+                                        fused_step=fused)
+    legs = {}
+    for name, lm in lms.items():
+        legs[f"{name}_one"] = lambda lm=lm: lm.generate(prompts[:1], new_tokens, graph=True)
+        legs[f"{name}_batch"] = lambda lm=lm: lm.generate(prompts, new_tokens, graph=True)
+        legs[f"{name}_batch_sampled"] = lambda lm=lm: lm.generate(prompts, new_tokens, graph=True, **sample)
+    out = {k: fn() for k, fn in legs.items()}  # warm-up: captures the graphs
+    nodes = {}
+    for name, lm in lms.items():
+        try:
+            nodes[name] = _graph_kernel_nodes(torch, lm)
+        except Exception as e:  # the profiler is optional: the count is then reported as missing
+            nodes[name] = f"not counted: {type(e).__name__}"
+    rate = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():  # alternated in one process
+            t0 = time.perf_counter()
+            toks = fn()
+            rate[k].append(sum(len(t) for t in toks) / (time.perf_counter() - t0))
+    med = {k: statistics.median(v) for k, v in rate.items()}
+    return {"n_positions": n_positions, "prompt_len": prompt_len, "new_tokens": new_tokens, "batch": batch,
+            "rounds": rounds, "kernels_per_replayed_step": nodes,
+            "greedy_ids_equal": {k: out[f"fused_{k}"] == out[f"unfused_{k}"] for k in ("one", "batch")},
+            **{f"{k}_tokens_per_s_median": v for k, v in med.items()},
+            **{f"{k}_tokens_per_s_best": max(v) for k, v in rate.items()},
+            **{f"fused_over_unfused_{k}": med[f"fused_{k}"] / med[f"unfused_{k}"]
+               for k in ("one", "batch", "batch_sampled")}}
+
+
+def fused_legs(args, torch, minitorch, _hip):
+    res = {"device": torch.cuda.get_device_name(0), "kernel": [], "generate": []}
+    for M, K, N in FUSED_SHAPES:
+        r = bench_fused_kernel(torch, minitorch, _hip, M, K, N, args.rounds, args.warmup)
+        print(json.dumps(r), flush=True)
+        res["kernel"].append(r)
+    if not args.skip_generate:
+        for npos, plen, new, batch, rounds in ((40, 8, 32, 8, 5), (1024, 768, 128, 8, 3)):
+            r = bench_generate_fused(torch, minitorch, npos, plen, new, batch, rounds)
+            print(json.dumps(r), flush=True)
+            res["generate"].append(r)
+    os.makedirs(os.path.dirname(args.fused_out), exist_ok=True)
+    with open(args.fused_out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--spec-legs", action="store_true",
@@ -1152,6 +1271,10 @@ def main():
     ap.add_argument("--rope-legs", action="store_true",
                     help="run the rotary-embedding legs instead, into --rope-out")
     ap.add_argument("--rope-out", default=os.path.join(ROOT, "profiles", "rope_bench.json"))
+    ap.add_argument("--fused-legs", action="store_true",
+                    help="the fused skinny linear against what it replaces, and generate(graph=True) with and "
+                         "without fused_step")
+    ap.add_argument("--fused-out", default=os.path.join(ROOT, "profiles", "fused_step_bench.json"))
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--skip-generate", action="store_true")
@@ -1163,6 +1286,8 @@ def main():
     from minitorch import _hip
     if args.lib:
         _hip.use_library(os.path.abspath(args.lib), allow_missing=True)
+    if args.fused_legs:
+        return fused_legs(args, torch, minitorch, _hip)
     if args.spec_legs:
         return spec_legs(args, torch, minitorch, _hip)
     if args.extend_src_legs:
