@@ -538,6 +538,47 @@ int mt_linear_rows(int G, const float* x, int64_t ldx, int64_t M, int64_t K, con
                    const float* const* bias, const float* const* residual, float* const* out,
                    int gelu_mask, void* stream);
 
+/* mt_linear_rows with a choice of normalisation and gated groups (a Llama-shaped block's step).
+ * Ranges, alignment and guarantees are mt_linear_rows', and so are the bits where both can be
+ * asked the same thing: norm = 1, eps = 1e-8 and glu_mask = 0 run the kernels mt_linear_rows runs.
+ * norm: 0 none (gamma and beta NULL); 1 LayerNorm with this eps (var = E[x^2] - mu^2 + eps);
+ *   2 RMSNorm, xh = gamma (x rstd), rstd = 1 / sqrt(E[x^2] + eps), beta NULL (mt_rmsnorm_fw's
+ *   formula; the statistics are one wave's sums per row, as LayerNorm's).
+ * glu_mask bit g: group g is gated. W_g is [K, 2 N_g], the N_g gate columns then the N_g up
+ *   columns, bias_g has 2 N_g entries, and
+ *     out_g [M, N_g] = silu(xh @ W_gate + b_gate) * (xh @ W_up + b_up) (+ residual_g),
+ *   silu(u) = u / (1 + expf(-u)) as mt_swiglu_fw. N_g <= 2^30 - 32 for such a group. A workgroup
+ *   owns 32 output columns of it: the 64 columns of its tile are 32 gate columns and the 32 up
+ *   columns beside them, both halves of the same rows of W, so W is still read once and the
+ *   K loop is the ungated one; the epilogue pairs the halves. Row independence holds as above.
+ * Refused like mt_linear_rows, and also: norm outside 0..2; gamma or beta with norm = 0; norm = 1
+ * without both; norm = 2 without gamma or with a beta; eps < 0; glu_mask naming a group >= G; a
+ * group in both gelu_mask and glu_mask. */
+int mt_linear_rows_ex(int G, const float* x, int64_t ldx, int64_t M, int64_t K, int norm, const float* gamma,
+                      const float* beta, float eps, const float* const* W, const int64_t* N,
+                      const float* const* bias, const float* const* residual, float* const* out,
+                      int gelu_mask, int glu_mask, void* stream);
+
+/* ---- RMSNorm and SwiGLU (a Llama-shaped block's training path), device pointers (fp32) ----
+ * RMSNorm over the last dim of [rows, hidden]: rstd[r] = 1 / sqrt(mean_j x[r,j]^2 + eps),
+ * out = gamma (x rstd). Backward, with g = gamma dy: dx = rstd g - x rstd^3 (sum_j g_j x_j) / hidden,
+ * gamma_grad[j] = sum_r dy[r,j] x[r,j] rstd[r], reduced in two fixed stages through the workspace
+ * (mt_rmsnorm_bw_workspace_bytes), no atomics: deterministic. Any hidden; with hidden % 4 == 0,
+ * hidden <= 1024 and 16-byte aligned pointers a row is read once and held in registers.
+ * SwiGLU over gu [rows, 2F] = [a | b]: out [rows, F] = silu(a) b, silu(u) = u / (1 + expf(-u));
+ * backward dgu = [da | db], da = dout b s (1 + a (1 - s)) with s = sigmoid(a), db = dout silu(a).
+ * Any F >= 1 (16-byte accesses with F % 4 == 0 and aligned pointers, the same values otherwise).
+ * All are stream-ordered, allocate nothing and can be captured. Refused with a status and a
+ * mt_last_error() message before any device call: a NULL pointer, a size <= 0, eps < 0. */
+int mt_rmsnorm_fw(float* out, float* rstd, const float* inp, const float* gamma,
+                  int64_t rows, int64_t hidden, float eps, void* stream);
+int64_t mt_rmsnorm_bw_workspace_bytes(int64_t rows, int64_t hidden);
+int mt_rmsnorm_bw(float* gamma_grad, float* inp_grad, const float* out_grad, const float* inp,
+                  const float* gamma, const float* rstd, int64_t rows, int64_t hidden,
+                  void* workspace, void* stream);
+int mt_swiglu_fw(float* out, const float* gu, int64_t rows, int64_t F, void* stream);
+int mt_swiglu_bw(float* dgu, const float* dout, const float* gu, int64_t rows, int64_t F, void* stream);
+
 /* ---- FlashAttention, reference-compatible host pointers (fp32) ------------ */
 /* reference src/flashattention_kernel.cu:259 */
 void launch_flashattention_forward(float* Q, float* K, float* V, float* O, float* l, float* m,

@@ -32,6 +32,7 @@
 // count or of which epilogue stages are on.
 #include "../../include/minitorch_hip.h"
 #include "fa_common.h"
+#include "silu.h"
 #include <type_traits>
 
 namespace mt {
@@ -62,6 +63,10 @@ struct Args {
   int M, K;
   int gelu;  // bit g: GELU in group g's epilogue
   int vec;   // bit g: bias_g, residual_g and out_g take 16-B accesses (W: the kernel's VEC)
+  // read by the EXT instantiations only (mt_linear_rows_ex)
+  int glu;   // bit g: group g is gated (W_g [K, 2 N_g], a tile is 32 gate + 32 up columns)
+  int rms;   // gamma scales x * rstd (RMSNorm: no mean, beta unused)
+  float eps;
 };
 
 // the group's fields by comparison, never by a runtime index into the by-value struct (which
@@ -99,9 +104,31 @@ __device__ __forceinline__ float4 load_w(const float* __restrict__ W, int64_t N,
   for (int i = 0; i < 4; ++i) e[i] = row[col + i < N ? col + i : 0];
   return make_float4(e[0], e[1], e[2], e[3]);
 }
+// The same for a row of ld elements whose half starting at element `half` (0, or N of a gated
+// group: the up columns) holds the N columns addressed by col.
+template <bool VEC>
+__device__ __forceinline__ float4 load_w_half(const float* __restrict__ W, int64_t ld, int64_t half, int64_t N, int K,
+                                              int k, int64_t col) {
+  const float* row = W + (int64_t)min(k, K - 1) * ld + half;
+  if (VEC) return *(const float4*)(row + (col < N ? col : 0));  // N % 4 == 0, so half % 4 == 0 too
+  float e[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) e[i] = row[col + i < N ? col + i : 0];
+  return make_float4(e[0], e[1], e[2], e[3]);
+}
 
-// RB row blocks of 16 rows (M <= 16 RB), KS waves that split K, VEC: 16-byte loads of W
-template <int RB, int KS, bool VEC>
+// RB row blocks of 16 rows (M <= 16 RB), KS waves that split K, VEC: 16-byte loads of W.
+// EXT (mt_linear_rows_ex with RMSNorm, a gated group or an eps of its own): the same body with
+//  * the prologue's variance term E[x^2] + eps without the mean (a.rms), or LayerNorm's with a.eps;
+//  * gated groups (a.glu bit g): W_g is [K, 2 N], the workgroup's 64 tile columns are the 32 gate
+//    columns n0 .. n0 + 31 (lanes j < 8) and the 32 up columns N + n0 .. (lanes j >= 8) of the same
+//    row of W, so the K loop, the accumulators (acc[rb][c] of lane j: tile columns 4 j + c) and the
+//    K-split combine are untouched; the epilogue pairs column c of the summed tile with column
+//    c + 32: out[r][n0 + c] = silu(t[r][c] + bias[n0 + c]) * (t[r][c + 32] + bias[N + n0 + c])
+//    (+ residual), 8 threads of 4 columns per row.
+// Without EXT every EXT branch is compiled out: mt_linear_rows' instantiations are the ones
+// they were.
+template <int RB, int KS, bool VEC, bool EXT>
 __global__ __launch_bounds__(64 * KS) void linear_rows_kernel(const Args a) {
   constexpr int ROWS = 16 * RB;
   constexpr int SLOTS = KS > 1 ? KS - 1 : 1;  // partial tiles of waves 1.., slot 0 then the sum
@@ -116,17 +143,26 @@ __global__ __launch_bounds__(64 * KS) void linear_rows_kernel(const Args a) {
   const int tile0 = g == 0 ? 0 : (g == 1 ? a.tile_end[0] : a.tile_end[1]);
   const float* __restrict__ W = pick(a.W, g);
   const int64_t N = pick(a.N, g);
-  const int64_t n0 = (int64_t)(tile - tile0) * kTile;
+  const bool glu = EXT && ((a.glu >> g) & 1);
+  const int64_t n0 = (int64_t)(tile - tile0) * (glu ? kTile / 2 : kTile);
+  // this lane's 4 columns of W: of a gated group, gate columns for j < 8 and up columns above
+  const int64_t ldw = glu ? 2 * N : N, whalf = glu && j >= 8 ? N : 0;
+  const int64_t wcol = glu ? n0 + 4 * (j & 7) : n0 + 4 * j;
   const int M = a.M, K = a.K;
+  auto load = [&](int k) {
+    if constexpr (EXT) return load_w_half<VEC>(W, ldw, whalf, N, K, k, wcol);
+    else return load_w<VEC>(W, N, K, k, n0 + 4 * j);
+  };
   const int S = K / KS;           // this wave's k rows: [wave S, wave S + S)
   const int kw = wave * S;
   const int nch = (S + kChunk - 1) / kChunk;
   const bool ln = a.gamma != nullptr;
+  const bool rms = EXT && a.rms;  // RMSNorm: the same staging with mean 0 and no beta
 
   // the first chunk's W rows are on their way while the statistics are computed
   float4 wa[kSteps], wb[kSteps];
 #pragma unroll
-  for (int s = 0; s < kSteps; ++s) wa[s] = load_w<VEC>(W, N, K, kw + 4 * s + q, n0 + 4 * j);
+  for (int s = 0; s < kSteps; ++s) wa[s] = load(kw + 4 * s + q);
 
   if (ln) {
     // one wave per row, ln_fw_vec's sums: (x + y) + (z + w) per lane and 256 columns, then the
@@ -152,8 +188,8 @@ __global__ __launch_bounds__(64 * KS) void linear_rows_kernel(const Args a) {
         }
         s = wave_sum(s);
         ss = wave_sum(ss);
-        const float mean = s / (float)K;
-        const float var = ss / (float)K - mean * mean + kLnEps;
+        const float mean = rms ? 0.f : s / (float)K;
+        const float var = rms ? ss / (float)K + a.eps : ss / (float)K - mean * mean + (EXT ? a.eps : kLnEps);
         const int r = r0 + u * KS;
         if (lane == 0 && r < M) { stat[r][0] = mean; stat[r][1] = 1.f / sqrtf(var); }
       }
@@ -183,15 +219,18 @@ __global__ __launch_bounds__(64 * KS) void linear_rows_kernel(const Args a) {
 #pragma unroll
     for (int p = 0; p < ROWS / 8; ++p)
       xv[p] = *(const float4*)(a.x + (int64_t)min(8 * p + xr, M - 1) * a.ldx + kx);
-    const float4 gm = *(const float4*)((ln ? a.gamma : a.x) + kx), bt = *(const float4*)((ln ? a.beta : a.x) + kx);
+    const float4 gm = *(const float4*)((ln ? a.gamma : a.x) + kx), bt = *(const float4*)((ln && !rms ? a.beta : a.x) + kx);
     if constexpr (decltype(pf)::value) {
 #pragma unroll
-      for (int s = 0; s < kSteps; ++s) wb[s] = load_w<VEC>(W, N, K, kb + kChunk + 4 * s + q, n0 + 4 * j);
+      for (int s = 0; s < kSteps; ++s) wb[s] = load(kb + kChunk + 4 * s + q);
     }
 #pragma unroll
     for (int p = 0; p < ROWS / 8; ++p) {
       const int r = 8 * p + xr;
-      if (ln) {
+      if (rms) {
+        const float rsd = stat[min(r, M - 1)][1];
+        xv[p] = make_float4(gm.x * (xv[p].x * rsd), gm.y * (xv[p].y * rsd), gm.z * (xv[p].z * rsd), gm.w * (xv[p].w * rsd));
+      } else if (ln) {
         const float mean = stat[min(r, M - 1)][0], rsd = stat[min(r, M - 1)][1];
         xv[p] = make_float4(gm.x * ((xv[p].x - mean) * rsd) + bt.x, gm.y * ((xv[p].y - mean) * rsd) + bt.y,
                             gm.z * ((xv[p].z - mean) * rsd) + bt.z, gm.w * ((xv[p].w - mean) * rsd) + bt.w);
@@ -255,6 +294,40 @@ __global__ __launch_bounds__(64 * KS) void linear_rows_kernel(const Args a) {
   const float* __restrict__ res = pick(a.res, g);
   float* __restrict__ out = pick(a.out, g);
   const bool gelu = (a.gelu >> g) & 1, vec_io = (a.vec >> g) & 1;
+  if (glu) {  // 4 gate columns and their 4 up columns per thread and pass
+    for (int i = threadIdx.x; i < M * (kTile / 8); i += 64 * KS) {
+      const int r = i >> 3, c = 4 * (i & 7);
+      const int64_t col = n0 + c;
+      if (col >= N) continue;
+      const float4 ta = *(const float4*)(smem + r * kTile + c), tb = *(const float4*)(smem + r * kTile + kTile / 2 + c);
+      float va[4] = {ta.x, ta.y, ta.z, ta.w}, vb[4] = {tb.x, tb.y, tb.z, tb.w};
+      const int64_t o = (int64_t)r * N + col;
+      if (vec_io) {
+        if (bias) {
+          const float4 ba = *(const float4*)(bias + col), bb = *(const float4*)(bias + N + col);
+          va[0] += ba.x; va[1] += ba.y; va[2] += ba.z; va[3] += ba.w;
+          vb[0] += bb.x; vb[1] += bb.y; vb[2] += bb.z; vb[3] += bb.w;
+        }
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = silu(va[e]) * vb[e];
+        if (res) { const float4 b = *(const float4*)(res + o); v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w; }
+        *(float4*)(out + o) = make_float4(v[0], v[1], v[2], v[3]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          if (col + e < N) {
+            float ua = va[e], ub = vb[e];
+            if (bias) { ua += bias[col + e]; ub += bias[N + col + e]; }
+            float u = silu(ua) * ub;
+            if (res) u += res[o + e];
+            out[o + e] = u;
+          }
+        }
+      }
+    }
+    return;
+  }
   for (int i = threadIdx.x; i < M * (kTile / 4); i += 64 * KS) {
     const int r = i >> 4;
     const int64_t col = n0 + 4 * (i & 15);
@@ -286,9 +359,14 @@ __global__ __launch_bounds__(64 * KS) void linear_rows_kernel(const Args a) {
 }
 
 template <int RB, int KS>
-static void launch(const Args& a, int tiles, bool vec, hipStream_t st) {
-  if (vec) hipLaunchKernelGGL((linear_rows_kernel<RB, KS, true>), dim3(tiles), dim3(64 * KS), 0, st, a);
-  else hipLaunchKernelGGL((linear_rows_kernel<RB, KS, false>), dim3(tiles), dim3(64 * KS), 0, st, a);
+static void launch(const Args& a, int tiles, bool vec, bool ext, hipStream_t st) {
+  if (ext) {
+    if (vec) hipLaunchKernelGGL((linear_rows_kernel<RB, KS, true, true>), dim3(tiles), dim3(64 * KS), 0, st, a);
+    else hipLaunchKernelGGL((linear_rows_kernel<RB, KS, false, true>), dim3(tiles), dim3(64 * KS), 0, st, a);
+  } else {
+    if (vec) hipLaunchKernelGGL((linear_rows_kernel<RB, KS, true, false>), dim3(tiles), dim3(64 * KS), 0, st, a);
+    else hipLaunchKernelGGL((linear_rows_kernel<RB, KS, false, false>), dim3(tiles), dim3(64 * KS), 0, st, a);
+  }
 }
 
 static bool overlap(const void* p, int64_t pbytes, const void* r, int64_t rbytes) {
@@ -301,55 +379,66 @@ static bool overlap(const void* p, int64_t pbytes, const void* r, int64_t rbytes
 using namespace mt;
 using namespace mt::lr;
 
-
-extern "C" int mt_linear_rows(int G, const float* x, int64_t ldx, int64_t M, int64_t K, const float* gamma,
-                              const float* beta, const float* const* W, const int64_t* N,
-                              const float* const* bias, const float* const* residual, float* const* out,
-                              int gelu_mask, void* stream) {
-  if (G < 1 || G > kMaxG) return set_error("mt_linear_rows: G=%d is outside 1..%d", G, kMaxG);
+// Both entries: fn names the caller in the messages. norm: 0 none, 1 LayerNorm, 2 RMSNorm.
+static int run(const char* fn, int G, const float* x, int64_t ldx, int64_t M, int64_t K, int norm, const float* gamma,
+               const float* beta, float eps, const float* const* W, const int64_t* N, const float* const* bias,
+               const float* const* residual, float* const* out, int gelu_mask, int glu_mask, void* stream) {
+  if (G < 1 || G > kMaxG) return set_error("%s: G=%d is outside 1..%d", fn, G, kMaxG);
   if (M < 1 || M > kMaxM)
-    return set_error("mt_linear_rows: M=%lld is outside 1..%d (the skinny kernel; use mt_matmul_f32)", (long long)M,
-                     kMaxM);
+    return set_error("%s: M=%lld is outside 1..%d (the skinny kernel; use mt_matmul_f32)", fn, (long long)M, kMaxM);
   if (K < 4 || K > kMaxK || K % 4)
-    return set_error("mt_linear_rows: K=%lld must be a multiple of 4 in 4..%d", (long long)K, kMaxK);
-  if (!x) return set_error("mt_linear_rows: x is NULL");
-  if (ldx < K || ldx % 4) return set_error("mt_linear_rows: ldx=%lld must be a multiple of 4 and >= K", (long long)ldx);
-  if (!W || !N || !out) return set_error("mt_linear_rows: the W, N or out array is NULL");
-  if ((gamma == nullptr) != (beta == nullptr)) return set_error("mt_linear_rows: gamma and beta are NULL together or not at all");
-  if ((uintptr_t)x & 15) return set_error("mt_linear_rows: x is misaligned (16 bytes)");
-  if (((uintptr_t)gamma | (uintptr_t)beta) & 15) return set_error("mt_linear_rows: gamma / beta are misaligned (16 bytes)");
-  if (gelu_mask < 0 || gelu_mask >> G) return set_error("mt_linear_rows: gelu_mask=%d names a group >= G=%d", gelu_mask, G);
+    return set_error("%s: K=%lld must be a multiple of 4 in 4..%d", fn, (long long)K, kMaxK);
+  if (!x) return set_error("%s: x is NULL", fn);
+  if (ldx < K || ldx % 4) return set_error("%s: ldx=%lld must be a multiple of 4 and >= K", fn, (long long)ldx);
+  if (!W || !N || !out) return set_error("%s: the W, N or out array is NULL", fn);
+  if (norm < 0 || norm > 2) return set_error("%s: norm=%d is outside 0..2 (none, LayerNorm, RMSNorm)", fn, norm);
+  if (norm == 0 && (gamma || beta)) return set_error("%s: norm=0 takes no gamma and no beta", fn);
+  if (norm == 1 && (!gamma || !beta)) return set_error("%s: gamma and beta are NULL together or not at all", fn);
+  if (norm == 2 && !gamma) return set_error("%s: RMSNorm (norm=2) needs gamma", fn);
+  if (norm == 2 && beta) return set_error("%s: RMSNorm (norm=2) has no beta", fn);
+  if (norm && !(eps >= 0.f)) return set_error("%s: eps=%g is negative", fn, (double)eps);
+  if ((uintptr_t)x & 15) return set_error("%s: x is misaligned (16 bytes)", fn);
+  if (((uintptr_t)gamma | (uintptr_t)beta) & 15) return set_error("%s: gamma / beta are misaligned (16 bytes)", fn);
+  if (gelu_mask < 0 || gelu_mask >> G) return set_error("%s: gelu_mask=%d names a group >= G=%d", fn, gelu_mask, G);
+  if (glu_mask < 0 || glu_mask >> G) return set_error("%s: glu_mask=%d names a group >= G=%d", fn, glu_mask, G);
+  if (gelu_mask & glu_mask)
+    return set_error("%s: gelu_mask=%d and glu_mask=%d share a group (GELU or the gate, not both)", fn, gelu_mask, glu_mask);
 
   Args a = {};
   a.x = x; a.gamma = gamma; a.beta = beta; a.ldx = ldx; a.M = (int)M; a.K = (int)K; a.gelu = gelu_mask;
+  a.glu = glu_mask; a.rms = norm == 2; a.eps = eps;
   const int64_t xbytes = ((M - 1) * ldx + K) * 4;
   int64_t tiles = 0;
   bool vec_all = true;
   for (int g = 0; g < G; ++g) {
-    if (N[g] < 1 || N[g] > (1ll << 31) - kTile)
-      return set_error("mt_linear_rows: N[%d]=%lld is outside 1..2^31-64", g, (long long)N[g]);
-    if (!W[g]) return set_error("mt_linear_rows: W[%d] is NULL", g);
-    if (!out[g]) return set_error("mt_linear_rows: out[%d] is NULL", g);
+    const bool glu = (glu_mask >> g) & 1;
+    // a gated group's row of W holds 2 N_g columns
+    if (N[g] < 1 || N[g] > ((1ll << 31) - kTile) / (glu ? 2 : 1))
+      return set_error("%s: N[%d]=%lld is outside 1..%s", fn, g, (long long)N[g], glu ? "2^30-32 (gated)" : "2^31-64");
+    if (!W[g]) return set_error("%s: W[%d] is NULL", fn, g);
+    if (!out[g]) return set_error("%s: out[%d] is NULL", fn, g);
     const float* b = bias ? bias[g] : nullptr;
     const float* r = residual ? residual[g] : nullptr;
     if (((uintptr_t)W[g] | (uintptr_t)out[g] | (uintptr_t)b | (uintptr_t)r) & 3)
-      return set_error("mt_linear_rows: a pointer of group %d is misaligned (4 bytes)", g);
+      return set_error("%s: a pointer of group %d is misaligned (4 bytes)", fn, g);
     const int64_t obytes = M * N[g] * 4;
-    if (overlap(out[g], obytes, x, xbytes)) return set_error("mt_linear_rows: out[%d] overlaps x", g);
+    if (overlap(out[g], obytes, x, xbytes)) return set_error("%s: out[%d] overlaps x", fn, g);
     for (int h = 0; h < G; ++h) {
       const float* rh = residual ? residual[h] : nullptr;
       if (rh && overlap(out[g], obytes, rh, M * N[h] * 4))
-        return set_error("mt_linear_rows: out[%d] overlaps residual[%d]", g, h);
+        return set_error("%s: out[%d] overlaps residual[%d]", fn, g, h);
       if (h < g && overlap(out[g], obytes, out[h], M * N[h] * 4))
-        return set_error("mt_linear_rows: out[%d] overlaps out[%d]", g, h);
+        return set_error("%s: out[%d] overlaps out[%d]", fn, g, h);
     }
     a.W[g] = W[g]; a.N[g] = N[g]; a.bias[g] = b; a.res[g] = r; a.out[g] = out[g];
+    // (N % 4 == 0 keeps a gated group's up half, N elements into the row and into the bias, aligned)
     const bool vw = N[g] % 4 == 0 && !((uintptr_t)W[g] & 15);
     const bool vio = N[g] % 4 == 0 && !(((uintptr_t)out[g] | (uintptr_t)b | (uintptr_t)r) & 15);
     vec_all = vec_all && vw;
     a.vec |= (vio ? 1 : 0) << g;
-    tiles += (N[g] + kTile - 1) / kTile;
-    if (tiles > (1ll << 30)) return set_error("mt_linear_rows: too many column tiles");
+    const int width = glu ? kTile / 2 : kTile;  // output columns per workgroup
+    tiles += (N[g] + width - 1) / width;
+    if (tiles > (1ll << 30)) return set_error("%s: too many column tiles", fn);
     a.tile_end[g] = (int)tiles;
   }
   for (int g = G; g < kMaxG; ++g) a.tile_end[g] = 0x7fffffff;
@@ -357,15 +446,35 @@ extern "C" int mt_linear_rows(int G, const float* x, int64_t ldx, int64_t M, int
   const int ks = K % 16 == 0 ? 4 : 1;  // the plan: a function of K alone (the tile is 64 columns always)
   const hipStream_t st = (hipStream_t)stream;
   const int rb = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
+  // What mt_linear_rows can ask for runs on the instantiations it always had, whichever entry asks.
+  const bool ext = norm == 2 || glu_mask != 0 || (norm == 1 && eps != kLnEps);
   // 16-byte loads of W in a launch where every group allows them (a property of N and the pointers)
   if (ks == 4) {
-    if (rb == 1) launch<1, 4>(a, (int)tiles, vec_all, st);
-    else if (rb == 2) launch<2, 4>(a, (int)tiles, vec_all, st);
-    else launch<4, 4>(a, (int)tiles, vec_all, st);
+    if (rb == 1) launch<1, 4>(a, (int)tiles, vec_all, ext, st);
+    else if (rb == 2) launch<2, 4>(a, (int)tiles, vec_all, ext, st);
+    else launch<4, 4>(a, (int)tiles, vec_all, ext, st);
   } else {
-    if (rb == 1) launch<1, 1>(a, (int)tiles, vec_all, st);
-    else if (rb == 2) launch<2, 1>(a, (int)tiles, vec_all, st);
-    else launch<4, 1>(a, (int)tiles, vec_all, st);
+    if (rb == 1) launch<1, 1>(a, (int)tiles, vec_all, ext, st);
+    else if (rb == 2) launch<2, 1>(a, (int)tiles, vec_all, ext, st);
+    else launch<4, 1>(a, (int)tiles, vec_all, ext, st);
   }
-  return check_hip(hipGetLastError(), "mt_linear_rows");
+  return check_hip(hipGetLastError(), fn);
+}
+
+extern "C" int mt_linear_rows_ex(int G, const float* x, int64_t ldx, int64_t M, int64_t K, int norm, const float* gamma,
+                                 const float* beta, float eps, const float* const* W, const int64_t* N,
+                                 const float* const* bias, const float* const* residual, float* const* out,
+                                 int gelu_mask, int glu_mask, void* stream) {
+  return run("mt_linear_rows_ex", G, x, ldx, M, K, norm, gamma, beta, eps, W, N, bias, residual, out, gelu_mask,
+             glu_mask, stream);
+}
+
+extern "C" int mt_linear_rows(int G, const float* x, int64_t ldx, int64_t M, int64_t K, const float* gamma,
+                              const float* beta, const float* const* W, const int64_t* N,
+                              const float* const* bias, const float* const* residual, float* const* out,
+                              int gelu_mask, void* stream) {
+  if ((gamma == nullptr) != (beta == nullptr))
+    return set_error("mt_linear_rows: gamma and beta are NULL together or not at all");
+  return run("mt_linear_rows", G, x, ldx, M, K, gamma ? 1 : 0, gamma, beta, kLnEps, W, N, bias, residual, out, gelu_mask,
+             0, stream);
 }

@@ -105,6 +105,13 @@ _PROTOS = {
     "mt_rope": (_int, [_int, _int, _vp, _vp, _i64, _i64p, _i64p, _vp, _vp, _i64, _i64p, _i64p,
                        _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "mt_linear_rows": (_int, [_int, _vp, _i64, _i64, _i64, _vp, _vp, _vpp, _i64p, _vpp, _vpp, _vpp, _int, _vp]),
+    "mt_linear_rows_ex": (_int, [_int, _vp, _i64, _i64, _i64, _int, _vp, _vp, ctypes.c_float, _vpp, _i64p, _vpp, _vpp,
+                                 _vpp, _int, _int, _vp]),
+    "mt_rmsnorm_fw": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_float, _vp]),
+    "mt_rmsnorm_bw_workspace_bytes": (_i64, [_i64, _i64]),
+    "mt_rmsnorm_bw": (_int, [_vp] * 6 + [_i64, _i64, _vp, _vp]),
+    "mt_swiglu_fw": (_int, [_vp, _vp, _i64, _i64, _vp]),
+    "mt_swiglu_bw": (_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "mt_attn_softmax_fw": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64p, _int, _vp]),
     "mt_attn_softmax_bw": (_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "mt_layernorm_fw": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
@@ -1069,13 +1076,18 @@ fused_linear_calls = 0  # launches of mt_linear_rows through fused_linear (tests
 
 
 def fused_linear(x, weights, biases=None, residuals=None, gamma=None, beta=None, gelu=False, outs=None,
-                 stream: Optional[int] = None):
-    """The fused skinny linear (mt_linear_rows; fp32): out_g = epilogue_g(prologue(x) @ W_g) for the
-    1..3 weights W_g [K, N_g] (dense) over the shared x [M <= 64, K] (unit-stride rows), one launch.
-    gamma / beta [K]: LayerNorm x first (both or neither). biases / residuals: None, or one entry
-    per weight ([N_g] / dense [M, N_g]; None entries skip the stage). gelu: a bool for all groups
-    or one per group (GELU_tanh after the bias). outs: dense [M, N_g] tensors to write into
-    (allocated when None). Returns the list of outputs. Inference only."""
+                 stream: Optional[int] = None, norm=None, eps=None, glu=False):
+    """The fused skinny linear (mt_linear_rows / mt_linear_rows_ex; fp32): out_g =
+    epilogue_g(prologue(x) @ W_g) for the 1..3 weights W_g (dense) over the shared x [M <= 64, K]
+    (unit-stride rows), one launch.
+    norm: None (LayerNorm when gamma and beta are given, else nothing), "layer" (gamma and beta
+    [K]) or "rms" (gamma [K] alone: gamma (x rstd)); eps: the variance term's (None: 1e-8 for
+    LayerNorm, mt_layernorm_fw's; 1e-5 for RMSNorm). biases / residuals: None, or one entry per
+    weight (None entries skip the stage). gelu: a bool for all groups or one per group (GELU_tanh
+    after the bias). glu: the same for the gate: such a group's weight is [K, 2 N_g] (gate
+    columns, then up columns), its bias [2 N_g], and out_g [M, N_g] = silu(gate) * up (+ residual).
+    Ungated weights are [K, N_g], biases [N_g]; residuals and outs are dense [M, N_g]. outs:
+    tensors to write into (allocated when None). Returns the list of outputs. Inference only."""
     global fused_linear_calls
     torch = _torch()
     G = len(weights)
@@ -1086,35 +1098,53 @@ def fused_linear(x, weights, biases=None, residuals=None, gamma=None, beta=None,
     for name, group in (("biases", biases), ("residuals", residuals), ("outs", outs)):
         if group is not None and len(group) != G:
             raise ValueError(f"fused_linear: {name} has {len(group)} entries for {G} weights")
-    if (gamma is None) != (beta is None):
+    if norm not in (None, "layer", "rms"):
+        raise ValueError(f'fused_linear: norm must be None, "layer" or "rms", got {norm!r}')
+    if norm == "rms":
+        if gamma is None or beta is not None:
+            raise ValueError('fused_linear: norm="rms" takes gamma and no beta')
+    elif (gamma is None) != (beta is None):
         raise ValueError("fused_linear: gamma and beta go together")
+    elif norm == "layer" and gamma is None:
+        raise ValueError('fused_linear: norm="layer" needs gamma and beta')
     for name, t in (("gamma", gamma), ("beta", beta)):
         if t is not None and (t.dtype != torch.float32 or t.numel() != K or not t.is_contiguous() or not t.is_cuda):
             raise ValueError(f"fused_linear: {name} must be a dense device float32 [{K}] tensor")
-    gelu = [bool(gelu)] * G if isinstance(gelu, (bool, int)) else [bool(v) for v in gelu]
-    if len(gelu) != G:
-        raise ValueError(f"fused_linear: gelu has {len(gelu)} entries for {G} weights")
+    flags = lambda v, name: [bool(v)] * G if isinstance(v, (bool, int)) else [bool(e) for e in v]  # noqa: E731
+    gelu, glu = flags(gelu, "gelu"), flags(glu, "glu")
+    for name, v in (("gelu", gelu), ("glu", glu)):
+        if len(v) != G:
+            raise ValueError(f"fused_linear: {name} has {len(v)} entries for {G} weights")
     biases = [None] * G if biases is None else list(biases)
     residuals = [None] * G if residuals is None else list(residuals)
     outs = [None] * G if outs is None else list(outs)
+    ns = []
     for g, w in enumerate(weights):
-        if w.dim() != 2 or w.shape[0] != K or w.dtype != torch.float32 or not w.is_contiguous():
-            raise ValueError(f"fused_linear: weight {g} must be a dense float32 [{K}, N] tensor, got {tuple(w.shape)}")
-        n = w.shape[1]
-        for name, t, shape in (("bias", biases[g], (n,)), ("residual", residuals[g], (M, n)), ("out", outs[g], (M, n))):
+        if w.dim() != 2 or w.shape[0] != K or w.dtype != torch.float32 or not w.is_contiguous() or (glu[g] and w.shape[1] % 2):
+            raise ValueError(f"fused_linear: weight {g} must be a dense float32 [{K}, {'2 N' if glu[g] else 'N'}] tensor, "
+                             f"got {tuple(w.shape)}")
+        n = w.shape[1] // 2 if glu[g] else w.shape[1]
+        ns.append(n)
+        for name, t, shape in (("bias", biases[g], (w.shape[1],)), ("residual", residuals[g], (M, n)), ("out", outs[g], (M, n))):
             if t is None:
                 continue
-            if t.dtype != torch.float32 or t.numel() != (n if len(shape) == 1 else M * n) or not t.is_contiguous() or not t.is_cuda:
+            if t.dtype != torch.float32 or t.numel() != shape[0] * (shape[1] if len(shape) > 1 else 1) or not t.is_contiguous() or not t.is_cuda:
                 raise ValueError(f"fused_linear: {name} {g} must be a dense device float32 {list(shape)} tensor")
         if outs[g] is None:
             outs[g] = torch.empty((M, n), dtype=torch.float32, device=x.device)
     ptrs = lambda ts: (ctypes.c_void_p * G)(*[None if t is None else t.data_ptr() for t in ts])  # noqa: E731
-    mask = sum(1 << g for g in range(G) if gelu[g])
+    mask = lambda v: sum(1 << g for g in range(G) if v[g])  # noqa: E731
     st = stream_ptr(x.device) if stream is None else stream
-    check(lib().mt_linear_rows(
-        G, x.data_ptr(), x.stride(0) if M > 1 else K, M, K, None if gamma is None else gamma.data_ptr(),
-        None if beta is None else beta.data_ptr(), ptrs(weights), (ctypes.c_int64 * G)(*[w.shape[1] for w in weights]),
-        ptrs(biases), ptrs(residuals), ptrs(outs), mask, st), "mt_linear_rows")
+    head = (G, x.data_ptr(), x.stride(0) if M > 1 else K, M, K)
+    tail = (ptrs(weights), (ctypes.c_int64 * G)(*ns), ptrs(biases), ptrs(residuals), ptrs(outs), mask(gelu))
+    gp, bp = None if gamma is None else gamma.data_ptr(), None if beta is None else beta.data_ptr()
+    if norm != "rms" and eps is None and not any(glu):
+        check(lib().mt_linear_rows(*head, gp, bp, *tail, st), "mt_linear_rows")
+    else:
+        mode = 2 if norm == "rms" else (0 if gamma is None else 1)
+        if eps is None:
+            eps = 1e-5 if mode == 2 else 1e-8
+        check(lib().mt_linear_rows_ex(*head, mode, gp, bp, float(eps), *tail, mask(glu), st), "mt_linear_rows_ex")
     fused_linear_calls += 1
     return outs
 

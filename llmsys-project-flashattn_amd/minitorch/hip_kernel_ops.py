@@ -434,6 +434,46 @@ class HipKernelOps(TensorOps):
         return dx, dgamma, dbeta
 
     @staticmethod
+    def rmsnorm_fw(inp: Tensor, gamma: Tensor, eps: float):
+        """(gamma (x rstd), rstd [rows]) over the rows of a 2-D inp (mt_rmsnorm_fw)."""
+        x, gm = _dense(inp), _dense(gamma)
+        rows, H = x.shape
+        out, rstd = _out(x, x.shape), _out(x, (rows,))
+        _hip.check(_hip.lib().mt_rmsnorm_fw(_ptr(out), _ptr(rstd), _ptr(x), _ptr(gm), rows, H, float(eps), _stream()),
+                   "rmsnorm_fw")
+        return out, rstd
+
+    @staticmethod
+    def rmsnorm_bw(out_grad: Tensor, inp: Tensor, gamma: Tensor, rstd: Tensor):
+        """(inp_grad, gamma_grad [1, H]) of rmsnorm_fw (mt_rmsnorm_bw)."""
+        import torch
+        g, x, gm = _dense(out_grad), _dense(inp), _dense(gamma)
+        rows, H = x.shape
+        dx, dgamma = _out(x, x.shape), _out(x, (1, H))
+        ws = torch.empty(max(1, _hip.lib().mt_rmsnorm_bw_workspace_bytes(rows, H) // 4), dtype=torch.float32,
+                         device="cuda")
+        _hip.check(_hip.lib().mt_rmsnorm_bw(_ptr(dgamma), _ptr(dx), _ptr(g), _ptr(x), _ptr(gm), _ptr(rstd), rows, H,
+                                            ws.data_ptr(), _stream()), "rmsnorm_bw")
+        return dx, dgamma
+
+    @staticmethod
+    def swiglu_fw(gu: Tensor) -> Tensor:
+        """silu(a) * b over gu [rows, 2F] = [a | b] (mt_swiglu_fw)."""
+        gu = _dense(gu)
+        rows, F2 = gu.shape
+        out = _out(gu, (rows, F2 // 2))
+        _hip.check(_hip.lib().mt_swiglu_fw(_ptr(out), _ptr(gu), rows, F2 // 2, _stream()), "swiglu_fw")
+        return out
+
+    @staticmethod
+    def swiglu_bw(out_grad: Tensor, gu: Tensor) -> Tensor:
+        g, gu = _dense(out_grad), _dense(gu)
+        rows, F2 = gu.shape
+        dgu = _out(gu, (rows, F2))
+        _hip.check(_hip.lib().mt_swiglu_bw(_ptr(dgu), _ptr(g), _ptr(gu), rows, F2 // 2, _stream()), "swiglu_bw")
+        return dgu
+
+    @staticmethod
     def _kv(kv_len):
         """A [B] key-padding length tensor (minitorch Tensor, device storage) as the int32
         device vector the C ABI takes, or None."""
@@ -703,17 +743,20 @@ class HipKernelOps(TensorOps):
         return res[0] if x2 is None else (res[0], res[1])
 
     @staticmethod
-    def fused_linear(x: Tensor, weights, biases=None, residuals=None, ln=None, gelu=False):
-        """The fused skinny linear of a cached decode step (mt_linear_rows): for the 1..3 dense
-        weights W_g [K, N_g] over the shared x [M <= 64, K], out_g = (+ residual_g)(GELU)(+ bias_g)
-        (LayerNorm(x) @ W_g) in one launch. ln: (gamma, beta) to normalise x first, or None;
-        biases / residuals: None or one entry per weight (None entries skip the stage); gelu: one
-        bool, or one per weight. Returns the list of new [M, N_g] tensors (no history: inference
-        only)."""
+    def fused_linear(x: Tensor, weights, biases=None, residuals=None, ln=None, gelu=False, norm=None, eps=None,
+                     glu=False):
+        """The fused skinny linear of a cached decode step (mt_linear_rows / mt_linear_rows_ex): for
+        the 1..3 dense weights W_g [K, N_g] over the shared x [M <= 64, K], out_g = (+ residual_g)
+        (GELU)(+ bias_g)(norm(x) @ W_g) in one launch. ln: (gamma, beta) to LayerNorm x first,
+        (gamma,) or (gamma, None) with norm="rms" for RMSNorm, or None; eps: the norm's (None: the
+        kernels' defaults). biases / residuals: None or one entry per weight (None entries skip the
+        stage); gelu, glu: one bool, or one per weight (glu: the weight is [K, 2 N_g] and out_g =
+        silu(gate) * up). Returns the list of new [M, N_g] tensors (no history: inference only)."""
         dense = lambda t: None if t is None else _torch_view(_dense(t))  # noqa: E731
         group = lambda ts: None if ts is None else [dense(t) for t in ts]  # noqa: E731
         xv = _torch_view(x if x._tensor.strides[-1] == 1 else x.contiguous())
+        beta = None if ln is None or len(ln) < 2 or ln[1] is None else dense(ln[1]).reshape(-1)
         outs = _hip.fused_linear(xv, [dense(w) for w in weights], group(biases), group(residuals),
                                  gamma=None if ln is None else dense(ln[0]).reshape(-1),
-                                 beta=None if ln is None else dense(ln[1]).reshape(-1), gelu=gelu)
+                                 beta=beta, gelu=gelu, norm=norm, eps=eps, glu=glu)
         return [_wrap(o.reshape(-1), o.shape, x.backend) for o in outs]

@@ -103,3 +103,21 @@ class FusedLayerNorm(Module):
 
     def forward(self, x: Tensor) -> Tensor:
         return x.layernorm(self.weights.value, self.bias.value)
+
+
+class FusedRMSNorm(Module):
+    """RMSNorm, gamma (x / sqrt(mean x^2 + eps)): Tensor.rmsnorm, the HIP kernel where the backend
+    has it and tensor ops otherwise."""
+
+    def __init__(self, n_embd: int, eps: float, backend):
+        super().__init__()
+        self.n_embd = n_embd
+        self.eps = eps
+        self.weights = Parameter(ones((n_embd,), backend=backend))
+
+    @property
+    def gamma(self) -> Tensor:
+        return self.weights.value
+
+    def forward(self, x: Tensor) -> Tensor:
+        return x.rmsnorm(self.weights.value, self.eps)

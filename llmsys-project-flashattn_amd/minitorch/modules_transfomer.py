@@ -18,7 +18,7 @@ import weakref
 import numpy as np
 
 from .module import Module
-from .modules_basic import Dropout, Embedding, FusedLayerNorm, LayerNorm1d, Linear
+from .modules_basic import Dropout, Embedding, FusedLayerNorm, FusedRMSNorm, LayerNorm1d, Linear
 from .nn import GELU, softmax
 from .rotary import RotaryTable, apply_rope
 from .tensor_functions import tensor, tensor_from_numpy
@@ -87,6 +87,22 @@ FUSED_STEP_MAX_WIDTH = 1024
 
 def _bias(linear):
     return None if linear.bias is None else linear.bias.value
+
+
+def _norm_kw(ln):
+    """The fused skinny linear's prologue arguments for a block's norm module: FusedLayerNorm's
+    (gamma, beta), or FusedRMSNorm's gamma with its eps."""
+    if isinstance(ln, FusedRMSNorm):
+        return dict(ln=(ln.gamma, None), norm="rms", eps=ln.eps)
+    return dict(ln=(ln.gamma, ln.beta))
+
+
+def _make_norm(norm: str, n_embd: int, ln_eps: float, backend, use_fused_kernel: bool):
+    if norm not in ("layer", "rms"):
+        raise ValueError(f'norm must be "layer" or "rms", got {norm!r}')
+    if norm == "rms":
+        return FusedRMSNorm(n_embd, ln_eps, backend)
+    return FusedLayerNorm(n_embd, backend) if use_fused_kernel else LayerNorm1d(n_embd, ln_eps, backend)
 
 
 def _takes_fused_step(module, rows: int, width: int, backend, p_dropout: float) -> bool:
@@ -238,7 +254,7 @@ class MultiHeadAttention(Module):
         proj = (self.q_projection, self.k_projection, self.v_projection)
         biases = [_bias(p) for p in proj]
         q, k, v = flat.fused_linear([p.weights.value for p in proj], None if biases[0] is None else biases,
-                                    ln=(ln.gamma, ln.beta))
+                                    **_norm_kw(ln))
         shp = (batch_size, seq_len, self.n_head, self.attn_hidden_dim)
         kv_shp = (batch_size, seq_len, self.n_kv_head, self.attn_hidden_dim)
         q, k, v = q.view(*shp).permute(0, 2, 1, 3), k.view(*kv_shp).permute(0, 2, 1, 3), v.view(*kv_shp).permute(0, 2, 1, 3)
@@ -355,10 +371,16 @@ class MultiHeadAttention(Module):
 
 class FeedForward(Module):
     def __init__(self, n_embd: int, middle_dim: int = 256, p_dropout: float = 0.1, bias: bool = True,
-                 backend=None, fused_step: bool = False):
+                 backend=None, fused_step: bool = False, activation: str = "gelu"):
+        """activation: "gelu" is linear_in -> GELU -> linear_out (the reference's); "swiglu" the
+        gated MLP: linear_in is [n_embd, 2 middle_dim], its first middle_dim columns the gate and
+        the rest the up projection, and linear_out takes silu(gate) * up (Tensor.swiglu)."""
         super().__init__()
+        if activation not in ("gelu", "swiglu"):
+            raise ValueError(f'activation must be "gelu" or "swiglu", got {activation!r}')
+        self.activation = activation
         self.fused_step = bool(fused_step)
-        self.linear_in = Linear(n_embd, middle_dim, bias=bias, backend=backend)
+        self.linear_in = Linear(n_embd, middle_dim * (2 if activation == "swiglu" else 1), bias=bias, backend=backend)
         self.linear_out = Linear(middle_dim, n_embd, bias=bias, backend=backend)
         self.dropout = Dropout(p_dropout)
 
@@ -366,7 +388,9 @@ class FeedForward(Module):
         batch_size, seq_len, n_embd = x.shape
         flat = x.view(batch_size * seq_len, n_embd)
         be = x.backend
-        if (getattr(be, "bias_gelu_fw", None) is not None and self.linear_in.bias is not None
+        if self.activation == "swiglu":
+            h = self.linear_in(flat).swiglu()
+        elif (getattr(be, "bias_gelu_fw", None) is not None and self.linear_in.bias is not None
                 and x._tensor.on_device):
             # linear_in's bias add and the GELU as one kernel each way (BiasGelu)
             from .tensor_functions import BiasGelu
@@ -378,10 +402,11 @@ class FeedForward(Module):
 
     def forward_fused(self, flat, ln):
         """forward for a cached step on the fused skinny linear: flat [rows, n_embd] is the
-        un-normalised input; linear_in takes ln (the block's FusedLayerNorm), its bias and the
-        GELU in one launch, linear_out its bias and the residual flat in another. Returns
+        un-normalised input; linear_in takes ln (the block's FusedLayerNorm or FusedRMSNorm), its
+        bias and the GELU (or the gate) in one launch, linear_out its bias and the residual flat in another. Returns
         [rows, n_embd]: ff(ln(flat)) + flat (no dropout: the caller checked)."""
-        h = flat.fused_linear(self.linear_in.weights.value, _bias(self.linear_in), ln=(ln.gamma, ln.beta), gelu=True)
+        glu = self.activation == "swiglu"  # the gate and the up half in the one launch
+        h = flat.fused_linear(self.linear_in.weights.value, _bias(self.linear_in), gelu=not glu, glu=glu, **_norm_kw(ln))
         return h.fused_linear(self.linear_out.weights.value, _bias(self.linear_out), residual=flat)
 
 
@@ -391,8 +416,10 @@ class TransformerLayer(Module):
     def __init__(self, n_embd: int, n_head: int, p_dropout: float = 0.1, ln_eps: float = 1e-8,
                  bias: bool = True, backend=None, use_fused_kernel: bool = False,
                  use_flash_attention: bool = False, causal: bool = True, n_kv_head=None, rope=None,
-                 fused_step: bool = False):
-        """fused_step (needs use_fused_kernel=True: the layer norms must be FusedLayerNorm): a
+                 fused_step: bool = False, norm: str = "layer", mlp: str = "gelu"):
+        """norm: "layer" (LayerNorm) or "rms" (FusedRMSNorm with eps = ln_eps); mlp: "gelu" or
+        "swiglu" (FeedForward(activation=...)).
+        fused_step (needs use_fused_kernel=True: the layer norms must be FusedLayerNorm): a
         decode or extend step of at most 64 rows on a filled cache runs on the fused skinny linear
         (_forward_fused); the prefill, larger steps, live dropout and a call without a cache take
         the unfused path. Unset, nothing changes."""
@@ -407,14 +434,10 @@ class TransformerLayer(Module):
                                             use_fused_kernel=use_fused_kernel,
                                             use_flash_attention=use_flash_attention, n_kv_head=n_kv_head,
                                             rope=rope, fused_step=fused_step)
-        self.ff = FeedForward(n_embd, 256, p_dropout, bias, backend, fused_step=fused_step)
+        self.ff = FeedForward(n_embd, 256, p_dropout, bias, backend, fused_step=fused_step, activation=mlp)
         self.use_fused_kernel = use_fused_kernel
-        if use_fused_kernel:
-            self.ln_1 = FusedLayerNorm(n_embd, backend)
-            self.ln_2 = FusedLayerNorm(n_embd, backend)
-        else:
-            self.ln_1 = LayerNorm1d(n_embd, ln_eps, backend)
-            self.ln_2 = LayerNorm1d(n_embd, ln_eps, backend)
+        self.ln_1 = _make_norm(norm, n_embd, ln_eps, backend, use_fused_kernel)
+        self.ln_2 = _make_norm(norm, n_embd, ln_eps, backend, use_fused_kernel)
 
     def forward(self, x, kv_len=None, cache=None):
         batch_size, seq_len, x_dim = x.shape
@@ -450,8 +473,12 @@ class DecoderLM(Module):
                  p_dropout: float = 0.1, ln_eps: float = 1e-5, bias: bool = True, backend=None,
                  use_fused_kernel: bool = False, use_flash_attention: bool = False, n_layer: int = 4,
                  n_kv_head=None, pos_encoding: str = "learned", rope_theta: float = 10000.0,
-                 fused_step: bool = False):
-        """fused_step (needs use_fused_kernel=True; fixed at construction): every decode or extend
+                 fused_step: bool = False, norm: str = "layer", mlp: str = "gelu"):
+        """norm: "layer", or "rms" for RMSNorm (eps = ln_eps) in every block and before lm_head;
+        mlp: "gelu", or "swiglu" for the gated MLP silu(x W_gate) * (x W_up). With rope and
+        n_kv_head these make a Llama-shaped model; every path of the model (training, the cache,
+        fused_step, graph, speculate) takes them.
+        fused_step (needs use_fused_kernel=True; fixed at construction): every decode or extend
         step of at most 64 rows (batch x tokens) on a filled KV cache runs its linears on the fused
         skinny linear (Tensor.fused_linear, mt_linear_rows): per layer ln_1 + Q / K / V in one
         launch, the output projection with its bias and residual in one, ln_2 + linear_in + GELU in
@@ -487,7 +514,7 @@ class DecoderLM(Module):
             setattr(self, f"t_layer_{i + 1}", TransformerLayer(
                 n_embd, n_head, p_dropout, ln_eps, bias, backend,
                 use_fused_kernel=use_fused_kernel, use_flash_attention=use_flash_attention,
-                n_kv_head=n_kv_head, rope=self.rope, fused_step=fused_step))
+                n_kv_head=n_kv_head, rope=self.rope, fused_step=fused_step, norm=norm, mlp=mlp))
         self.dropout = Dropout(p_dropout)
         self.lm_head = Linear(n_embd, n_vocab, bias, backend)
         self.use_fused_kernel = use_fused_kernel
@@ -495,7 +522,7 @@ class DecoderLM(Module):
         self.n_positions = n_positions
         self.n_head = n_head
         self.n_kv_head = n_head if n_kv_head is None else n_kv_head
-        self.ln = FusedLayerNorm(n_embd, backend) if use_fused_kernel else LayerNorm1d(n_embd, ln_eps, backend)
+        self.ln = _make_norm(norm, n_embd, ln_eps, backend, use_fused_kernel)
         self.graph_captures = 0  # hipGraph captures of the decode step (generate(graph=True))
         self.spec_stats = None   # the last generate(speculate=...) call's counters
 
@@ -527,7 +554,7 @@ class DecoderLM(Module):
         """The final LayerNorm and lm_head over flat [rows, n_embd]; for a decode or extend step
         (step=True) of a fused_step model within the fused kernel's range, one launch."""
         if step and _takes_fused_step(self, flat.shape[0], self.n_embd, flat.backend, self.p_dropout):
-            return flat.fused_linear(self.lm_head.weights.value, _bias(self.lm_head), ln=(self.ln.gamma, self.ln.beta))
+            return flat.fused_linear(self.lm_head.weights.value, _bias(self.lm_head), **_norm_kw(self.ln))
         return self.lm_head(self.ln(flat))
 
     def new_cache(self, batch_size: int, kv_dtype=None, page_size=None, n_pages=None):

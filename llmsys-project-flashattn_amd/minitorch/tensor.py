@@ -19,7 +19,7 @@ from .tensor_data import TensorData, UserIndex, UserShape, datatype, shape_broad
 from .tensor_functions import (
     EQ, LT, Add, All, Attn_Softmax, Attn_Softmax_NoMask, Copy, Exp, FlashAttention,
     FlashAttentionCausal, Inv, IsClose, LayerNorm, Log, MatMul, Mul, Neg, Permute,
-    PowerScalar, ReLU, Sigmoid, Sum, Tanh, View, tensor_from_numpy,
+    PowerScalar, ReLU, RMSNorm, Sigmoid, Sum, SwiGLU, Tanh, View, tensor_from_numpy,
 )
 
 TensorLike = Union[float, int, "Tensor"]
@@ -372,20 +372,44 @@ class Tensor:
             raise NotImplementedError("this backend has no extend attention kernel")
         return fn(self, Kc, Vc, visible, q_len, causal)
 
-    def fused_linear(self, weight, bias=None, residual=None, ln=None, gelu=False):
+    def rmsnorm(self, gamma: "Tensor", eps: float = 1e-5) -> "Tensor":
+        """RMSNorm over the rows of self [rows, hidden]: gamma (x rstd), rstd = 1 / sqrt(mean x^2 +
+        eps): no mean and no beta. One kernel each way where the backend has it (the RMSNorm
+        Function), the same thing in tensor ops otherwise; differentiable in self and gamma."""
+        if getattr(self.backend, "rmsnorm_fw", None) is not None:
+            return RMSNorm.apply(self, gamma, self._const(eps))
+        ms = (self * self).mean(dim=1)
+        return gamma * (self / ((ms + eps) ** 0.5))
+
+    def swiglu(self) -> "Tensor":
+        """The gated activation over self [rows, 2F] = [a | b]: silu(a) * b [rows, F], silu(u) =
+        u sigmoid(u). One kernel each way where the backend has it (the SwiGLU Function), tensor
+        ops otherwise (the halves picked by constant masks); differentiable."""
+        if getattr(self.backend, "swiglu_fw", None) is not None:
+            return SwiGLU.apply(self)
+        rows, width = self.shape
+        halves = self.contiguous().view(rows, 2, width // 2)
+        pick = lambda v: (halves * Tensor.make(v, (1, 2, 1), backend=self.backend)).sum(1).view(rows, width // 2)  # noqa: E731
+        a, b = pick([1.0, 0.0]), pick([0.0, 1.0])
+        return a * a.sigmoid() * b
+
+    def fused_linear(self, weight, bias=None, residual=None, ln=None, gelu=False, norm=None, eps=None, glu=False):
         """Generation: self [M <= 64, K] through one launch of the fused skinny linear,
         (+ residual)(GELU_tanh)(+ bias)(LayerNorm(self) @ weight); ln: (gamma, beta) or None. weight
         may be a list of 1..3 weights that share self (Q, K and V), bias / residual / gelu then
-        lists too (or None / one bool); the result is then a list. Inference only: the result has
-        no history, whatever the inputs' (as flash_attention_decode's), so nothing differentiates
-        through it; a backend without the kernel raises."""
+        lists too (or None / one bool); the result is then a list. norm="rms" with ln=(gamma, None)
+        normalises by RMSNorm instead (eps: its epsilon); glu: the weight is [K, 2 N] (gate columns,
+        then up columns) and the result silu(gate) * up (+ residual). Inference only: the result
+        has no history, whatever the inputs' (as flash_attention_decode's), so nothing
+        differentiates through it; a backend without the kernel raises."""
         fn = getattr(self.backend, "fused_linear", None)
         if fn is None:
             raise NotImplementedError("this backend has no fused skinny linear kernel (HipKernelOps has)")
+        kw = {} if norm is None and eps is None and glu is False else dict(norm=norm, eps=eps, glu=glu)
         if isinstance(weight, (list, tuple)):
-            return fn(self, list(weight), bias, residual, ln, gelu)
+            return fn(self, list(weight), bias, residual, ln, gelu, **kw)
         return fn(self, [weight], None if bias is None else [bias], None if residual is None else [residual],
-                  ln, gelu)[0]
+                  ln, gelu, **kw)[0]
 
     def rope(self, table, pos0=None) -> "Tensor":
         """Rotary position embedding of the head rows of self [B,H,T,d] by a RotaryTable: token t

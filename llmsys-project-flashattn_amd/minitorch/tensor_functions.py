@@ -420,6 +420,37 @@ class LayerNorm(Function):
         return out_grad.f.layernorm_bw(out_grad, inp, gamma, beta, var, means)
 
 
+class RMSNorm(Function):
+    """gamma (x rstd) over the rows of a 2-D inp as one backend kernel each way (mt_rmsnorm_fw /
+    mt_rmsnorm_bw); eps travels as a constant one-element tensor and gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, inp, gamma, eps):
+        out, rstd = inp.f.rmsnorm_fw(inp, gamma, float(eps.item()))
+        ctx.save_for_backward(inp, gamma, rstd)
+        return out
+
+    @staticmethod
+    def backward(ctx, out_grad):
+        inp, gamma, rstd = ctx.saved_values
+        dx, dgamma = out_grad.f.rmsnorm_bw(out_grad, inp, gamma, rstd)
+        return dx, dgamma, 0.0
+
+
+class SwiGLU(Function):
+    """silu(a) * b over gu [rows, 2F] = [a | b] as one backend kernel each way (mt_swiglu_fw / bw)."""
+
+    @staticmethod
+    def forward(ctx, gu):
+        ctx.save_for_backward(gu)
+        return gu.f.swiglu_fw(gu)
+
+    @staticmethod
+    def backward(ctx, out_grad):
+        (gu,) = ctx.saved_values
+        return out_grad.f.swiglu_bw(out_grad, gu)
+
+
 def _kv_kw(kv):
     """The optional key-padding lengths (a [B] constant tensor) as the ops' keyword."""
     return {} if kv is None else {"kv_len": kv}

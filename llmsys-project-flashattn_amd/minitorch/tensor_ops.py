@@ -153,3 +153,8 @@ class TensorBackend:
         self.fused_linear = getattr(ops, "fused_linear", None)
         # rotary position embedding as one kernel (optional: a backend without it runs the tensor-op form)
         self.rope = getattr(ops, "rope", None)
+        # RMSNorm and SwiGLU as one kernel each way (optional: a backend without them runs tensor ops)
+        self.rmsnorm_fw = getattr(ops, "rmsnorm_fw", None)
+        self.rmsnorm_bw = getattr(ops, "rmsnorm_bw", None)
+        self.swiglu_fw = getattr(ops, "swiglu_fw", None)
+        self.swiglu_bw = getattr(ops, "swiglu_bw", None)

@@ -1187,7 +1187,81 @@ def _graph_kernel_nodes(torch, lm):
     return sum(1 for ev in prof.events() if ev.device_type.name == "CUDA")
 
 
-def bench_generate_fused(torch, minitorch, n_positions, prompt_len, new_tokens, batch, rounds):
+def _alternate(torch, legs, rounds, warmup, inner):
+    """Median and minimum seconds per call of each captured leg, the legs alternated in one process."""
+    for fn in legs.values():
+        for _ in range(warmup):
+            _timed(torch, fn, 1)
+    times = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():
+            times[k].append(_timed(torch, fn, 1) / inner)
+    return {**{f"{k}_s_median": statistics.median(v) for k, v in times.items()},
+            **{f"{k}_s_min": min(v) for k, v in times.items()}}
+
+
+def bench_llama_kernel(torch, minitorch, M, K, F, rounds, warmup, inner=32):
+    """The gated linear_in of a Llama-shaped block (RMSNorm + bias + GLU, W [K, 2F]) in one launch
+    of mt_linear_rows_ex against mt_rmsnorm_fw -> mt_matmul_f32 -> the bias add -> mt_swiglu_fw and
+    against a device copy of W's bytes, as bench_fused_kernel measures its pairs."""
+    hip = minitorch.TensorBackend(minitorch.HipKernelOps)
+    rng = np.random.default_rng(0)
+    t = lambda a: minitorch.tensor_from_numpy(np.ascontiguousarray(a, dtype=np.float32), hip)  # noqa: E731
+    x, gamma = t(rng.normal(0.5, 1, (M, K))), t(1 + 0.3 * rng.standard_normal(K))
+    W, b = t(rng.uniform(-K ** -0.5, K ** -0.5, (K, 2 * F))), t(rng.uniform(-K ** -0.5, K ** -0.5, 2 * F))
+    copy_src, copy_dst = torch.empty(2 * K * F, device="cuda"), torch.empty(2 * K * F, device="cuda")
+    legs = {"fused": _graph_of(torch, lambda i: x.fused_linear(W, b, ln=(gamma, None), norm="rms", eps=1e-5, glu=True), inner),
+            "unfused": _graph_of(torch, lambda i: (x.rmsnorm(gamma, 1e-5) @ W + b).swiglu(), inner),
+            "copy_of_W_bytes": _graph_of(torch, lambda i: copy_dst.copy_(copy_src), inner)}
+    out = {"M": M, "K": K, "F": F, "rounds": rounds, "calls_per_replay": inner, "W_bytes": 8 * K * F,
+           **_alternate(torch, legs, rounds, warmup, inner)}
+    out["unfused_over_fused"] = out["unfused_s_median"] / out["fused_s_median"]
+    return out
+
+
+def bench_rmsnorm_training(torch, minitorch, rows, hidden, rounds, warmup, inner=16):
+    """mt_rmsnorm_fw + mt_rmsnorm_bw against mt_layernorm_fw + mt_layernorm_bw at a training shape."""
+    hip = minitorch.TensorBackend(minitorch.HipKernelOps)
+    rng = np.random.default_rng(0)
+    t = lambda a: minitorch.tensor_from_numpy(np.ascontiguousarray(a, dtype=np.float32), hip)  # noqa: E731
+    x, dy = t(rng.normal(0.5, 1, (rows, hidden))), t(rng.standard_normal((rows, hidden)))
+    gamma, beta = t(1 + 0.3 * rng.standard_normal(hidden)), t(0.2 * rng.standard_normal(hidden))
+
+    def rms(i):
+        _, rstd = hip.rmsnorm_fw(x, gamma, 1e-5)
+        return hip.rmsnorm_bw(dy, x, gamma, rstd)
+
+    def layer(i):
+        _, var, mean = hip.layernorm_fw(x, gamma, beta)
+        return hip.layernorm_bw(dy, x, gamma, beta, var, mean)
+    legs = {"rmsnorm_fw_bw": _graph_of(torch, rms, inner), "layernorm_fw_bw": _graph_of(torch, layer, inner)}
+    out = {"rows": rows, "hidden": hidden, "rounds": rounds, "calls_per_replay": inner,
+           **_alternate(torch, legs, rounds, warmup, inner)}
+    out["rmsnorm_over_layernorm"] = out["rmsnorm_fw_bw_s_median"] / out["layernorm_fw_bw_s_median"]
+    return out
+
+
+def llama_legs(args, torch, minitorch, _hip):
+    res = {"device": torch.cuda.get_device_name(0), "kernel": [], "norm_training": [], "generate": []}
+    for M in (1, 8, 64):
+        r = bench_llama_kernel(torch, minitorch, M, 256, 256, args.rounds, args.warmup)
+        print(json.dumps(r), flush=True)
+        res["kernel"].append(r)
+    r = bench_rmsnorm_training(torch, minitorch, 128 * 40, 256, args.rounds, args.warmup)  # config 5: batch 128 x 40 tokens
+    print(json.dumps(r), flush=True)
+    res["norm_training"].append(r)
+    if not args.skip_generate:
+        llama = dict(norm="rms", mlp="swiglu", pos_encoding="rope", n_kv_head=2)
+        for npos, plen, new, batch, rounds in ((40, 8, 32, 8, 5), (1024, 768, 128, 8, 3)):
+            r = bench_generate_fused(torch, minitorch, npos, plen, new, batch, rounds, **llama)
+            print(json.dumps(r), flush=True)
+            res["generate"].append(r)
+    os.makedirs(os.path.dirname(args.llama_out), exist_ok=True)
+    with open(args.llama_out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+def bench_generate_fused(torch, minitorch, n_positions, prompt_len, new_tokens, batch, rounds, **model_kw):
     backend = minitorch.TensorBackend(minitorch.HipKernelOps)
     rng = np.random.default_rng(0)
     prompts = [[int(t) for t in rng.integers(0, 10000, prompt_len)] for _ in range(batch)]
@@ -1197,7 +1271,7 @@ def bench_generate_fused(torch, minitorch, n_positions, prompt_len, new_tokens, 
         np.random.seed(0)  # the same weights
         lms[name] = minitorch.DecoderLM(n_vocab=10000, n_embd=256, n_head=8, n_positions=n_positions, p_dropout=0.0,
                                         backend=backend, use_fused_kernel=True, use_flash_attention=True,
-                                        fused_step=fused)
+                                        fused_step=fused, **model_kw)
     legs = {}
     for name, lm in lms.items():
         legs[f"{name}_one"] = lambda lm=lm: lm.generate(prompts[:1], new_tokens, graph=True)
@@ -1218,7 +1292,7 @@ def bench_generate_fused(torch, minitorch, n_positions, prompt_len, new_tokens, 
             rate[k].append(sum(len(t) for t in toks) / (time.perf_counter() - t0))
     med = {k: statistics.median(v) for k, v in rate.items()}
     return {"n_positions": n_positions, "prompt_len": prompt_len, "new_tokens": new_tokens, "batch": batch,
-            "rounds": rounds, "kernels_per_replayed_step": nodes,
+            "rounds": rounds, **({"model": model_kw} if model_kw else {}), "kernels_per_replayed_step": nodes,
             "greedy_ids_equal": {k: out[f"fused_{k}"] == out[f"unfused_{k}"] for k in ("one", "batch")},
             **{f"{k}_tokens_per_s_median": v for k, v in med.items()},
             **{f"{k}_tokens_per_s_best": max(v) for k, v in rate.items()},
@@ -1275,6 +1349,10 @@ def main():
                     help="the fused skinny linear against what it replaces, and generate(graph=True) with and "
                          "without fused_step")
     ap.add_argument("--fused-out", default=os.path.join(ROOT, "profiles", "fused_step_bench.json"))
+    ap.add_argument("--llama-legs", action="store_true",
+                    help="the Llama-shaped block: the gated fused linear and RMSNorm against what they replace, and "
+                         "generate(graph=True) of DecoderLM(norm=\"rms\", mlp=\"swiglu\") with and without fused_step")
+    ap.add_argument("--llama-out", default=os.path.join(ROOT, "profiles", "llama_block_bench.json"))
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--skip-generate", action="store_true")
@@ -1288,6 +1366,8 @@ def main():
         _hip.use_library(os.path.abspath(args.lib), allow_missing=True)
     if args.fused_legs:
         return fused_legs(args, torch, minitorch, _hip)
+    if args.llama_legs:
+        return llama_legs(args, torch, minitorch, _hip)
     if args.spec_legs:
         return spec_legs(args, torch, minitorch, _hip)
     if args.extend_src_legs:
