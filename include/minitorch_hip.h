@@ -559,6 +559,50 @@ int mt_linear_rows_ex(int G, const float* x, int64_t ldx, int64_t M, int64_t K, 
                       const float* const* bias, const float* const* residual, float* const* out,
                       int gelu_mask, int glu_mask, void* stream);
 
+/* ---- weight-only quantised linear (the cached decode step on bf16 / fp8 / int4 weights) ----
+ * mt_linear_rows_ex with the weights of every group in one of three storage formats; x, the
+ * arithmetic (fp32 MFMA) and the outputs stay fp32. Each format defines a dequantised fp32
+ * matrix W' [K, ncols] (ncols = N, or 2 N for a gated weight), and everything is defined on W':
+ *   MT_W_BF16: round-to-nearest-even of W; W' is the 16 bits widened by shift. No scales.
+ *   MT_W_FP8:  OCP e4m3 codes and one fp32 scale per column: amax = max_k |W[k][n]|,
+ *              s = amax > 0 ? amax / 448 : 1, code = e4m3 round-to-nearest of W / s (fp32
+ *              division), W' = fp32(e4m3(code) * s): mt_kv_cache_append_quant's rule with a
+ *              column for a row. A column holding an inf or a NaN: NaN codes, NaN scale.
+ *              scales: fp32 [ncols].
+ *   MT_W_INT4: symmetric, one fp32 scale per column and group of 32 consecutive rows of K:
+ *              s = amax > 0 ? amax / 7 : 1, code = rint(W / s) (ties to even) clamped to [-7, 7],
+ *              a two's-complement nibble, W' = fp32((float)code * s). A group holding a
+ *              non-finite value: zero codes, NaN scale. scales: fp32 [K / 32, ncols].
+ * The codes live in a packed layout that only these entry points read (tile-major, 16 bytes per
+ * lane and k block, whole tiles of 64 columns; a gated weight is packed as 32 gate + 32 up columns
+ * per tile, so glu must be the same when packing and when multiplying);
+ * mt_weight_quant_bytes gives its size and the scales'. K must be a multiple of 128 in 128..1024.
+ *
+ * mt_weight_quant: fp32 W [K, ldw >= ncols] -> codes and scales, on the device, fixed reduction
+ *   trees, no atomics. mt_weight_dequant: W' [K, ncols] dense and, when codes_out is not NULL,
+ *   the codes [K, ncols] dense (uint16 bit patterns for bf16, uint8 e4m3 for fp8, int8 values for
+ *   int4).
+ * mt_linear_rows_wq: mt_linear_rows_ex's arguments, ranges, formulas and guarantees, with W[g]
+ *   the packed codes (16-byte aligned) and scales[g] the scales of group g (the array may be NULL
+ *   for bf16); one format per launch. The codes are widened in registers and the accumulation is
+ *   mt_linear_rows_ex's (one chain per wave in ascending k, ((p0 + p1) + p2) + p3), so out has
+ *   the bits of mt_linear_rows_ex on the W' that mt_weight_dequant writes.
+ * All are stream-ordered, allocate nothing and can be captured. Refused with a status and a
+ * mt_last_error() message before any device call: an unknown fmt, K % 128, K > 1024, NULL or
+ * misaligned codes, scales (fp8, int4) or outputs, ldw < ncols, and for mt_linear_rows_wq
+ * everything mt_linear_rows_ex refuses. */
+enum { MT_W_BF16 = 1, MT_W_FP8 = 2, MT_W_INT4 = 3 };
+int mt_weight_quant_bytes(int fmt, int64_t K, int64_t N, int glu, int64_t* code_bytes, int64_t* scale_bytes);
+int mt_weight_quant(int fmt, const float* W, int64_t ldw, int64_t K, int64_t N, int glu, void* codes,
+                    float* scales, void* stream);
+int mt_weight_dequant(int fmt, const void* codes, const float* scales, int64_t K, int64_t N, int glu,
+                      float* W_out, void* codes_out, void* stream);
+int mt_linear_rows_wq(int fmt, int G, const float* x, int64_t ldx, int64_t M, int64_t K, int norm,
+                      const float* gamma, const float* beta, float eps, const void* const* W,
+                      const float* const* scales, const int64_t* N, const float* const* bias,
+                      const float* const* residual, float* const* out, int gelu_mask, int glu_mask,
+                      void* stream);
+
 /* ---- RMSNorm and SwiGLU (a Llama-shaped block's training path), device pointers (fp32) ----
  * RMSNorm over the last dim of [rows, hidden]: rstd[r] = 1 / sqrt(mean_j x[r,j]^2 + eps),
  * out = gamma (x rstd). Backward, with g = gamma dy: dx = rstd g - x rstd^3 (sum_j g_j x_j) / hidden,

@@ -26,6 +26,9 @@ def __getattr__(name):
     if name == "HipKernelOps":
         from .hip_kernel_ops import HipKernelOps
         return HipKernelOps
+    if name == "QuantizedWeight":
+        from ._hip import QuantizedWeight
+        return QuantizedWeight
     raise AttributeError(name)
 
 

@@ -25,6 +25,11 @@ MT_BF16 = 1
 # storage formats of a quantised KV cache (kv_dtype of the mt_*_kvq / *_quant entry points)
 MT_KV_BF16 = 1
 MT_KV_FP8 = 2
+# storage formats of a weight-only quantised linear (fmt of the mt_weight_* / mt_linear_rows_wq entry points)
+MT_W_BF16 = 1
+MT_W_FP8 = 2
+MT_W_INT4 = 3
+WEIGHT_FORMATS = {"bf16": MT_W_BF16, "fp8": MT_W_FP8, "int4": MT_W_INT4}
 
 _lib = None
 _allow_missing = False  # use_library(path, allow_missing=True): an older build may lack the newest entry points
@@ -107,6 +112,11 @@ _PROTOS = {
     "mt_linear_rows": (_int, [_int, _vp, _i64, _i64, _i64, _vp, _vp, _vpp, _i64p, _vpp, _vpp, _vpp, _int, _vp]),
     "mt_linear_rows_ex": (_int, [_int, _vp, _i64, _i64, _i64, _int, _vp, _vp, ctypes.c_float, _vpp, _i64p, _vpp, _vpp,
                                  _vpp, _int, _int, _vp]),
+    "mt_weight_quant_bytes": (_int, [_int, _i64, _i64, _int, _i64p, _i64p]),
+    "mt_weight_quant": (_int, [_int, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
+    "mt_weight_dequant": (_int, [_int, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp]),
+    "mt_linear_rows_wq": (_int, [_int, _int, _vp, _i64, _i64, _i64, _int, _vp, _vp, ctypes.c_float, _vpp, _vpp, _i64p,
+                                 _vpp, _vpp, _vpp, _int, _int, _vp]),
     "mt_rmsnorm_fw": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_float, _vp]),
     "mt_rmsnorm_bw_workspace_bytes": (_i64, [_i64, _i64]),
     "mt_rmsnorm_bw": (_int, [_vp] * 6 + [_i64, _i64, _vp, _vp]),
@@ -1072,6 +1082,78 @@ def rope(x, cos, sin, pos0=None, inverse: bool = False, out=None, x2=None, out2=
     return out if x2 is None else (out, out2)
 
 
+def weight_quant_bytes(fmt: int, K: int, N: int, glu: bool = False):
+    """(code_bytes, scale_bytes) of an fp32 [K, N] weight ([K, 2 N] gated) stored in format fmt
+    (mt_weight_quant_bytes; raises where the library refuses K or fmt). No device call."""
+    cb, sb = ctypes.c_int64(), ctypes.c_int64()
+    if lib().mt_weight_quant_bytes(int(fmt), int(K), int(N), int(bool(glu)), ctypes.byref(cb), ctypes.byref(sb)):
+        raise ValueError(lib().mt_last_error().decode(errors="replace"))
+    return cb.value, sb.value
+
+
+class QuantizedWeight:
+    """A linear's weight in the packed storage of the weight-only quantised skinny linear
+    (mt_weight_quant): fmt "bf16", "fp8" or "int4"; K, N as fused_linear counts them (a gated
+    weight, glu=True, has 2 N columns: gate then up); codes (uint8 device buffer, the packed
+    layout) and scales (float32: fp8 [ncols], int4 [K / 32, ncols], None for bf16); nbytes: the
+    device bytes of both. fused_linear takes it in place of the fp32 weight."""
+
+    def __init__(self, fmt, K, N, glu, codes, scales):
+        self.fmt, self.K, self.N, self.glu, self.codes, self.scales = fmt, K, N, glu, codes, scales
+        self.nbytes = codes.numel() + (0 if scales is None else 4 * scales.numel())
+
+    @property
+    def ncols(self) -> int:
+        return 2 * self.N if self.glu else self.N
+
+    @classmethod
+    def from_tensor(cls, w, fmt: str, glu: bool = False, stream: Optional[int] = None) -> "QuantizedWeight":
+        """Quantise a dense device float32 [K, ncols] torch tensor (or a minitorch device Tensor)
+        on the device. K must be a multiple of 128 in 128..1024."""
+        torch = _torch()
+        if fmt not in WEIGHT_FORMATS:
+            raise ValueError(f'fmt must be "bf16", "fp8" or "int4", got {fmt!r}')
+        if not isinstance(w, torch.Tensor):
+            from .hip_kernel_ops import _dense, _torch_view
+            w = _torch_view(_dense(w))
+        if w.dim() != 2 or w.dtype != torch.float32 or not w.is_contiguous() or not w.is_cuda or (glu and w.shape[1] % 2):
+            raise ValueError(f"QuantizedWeight.from_tensor takes a dense device float32 [K, {'2 N' if glu else 'N'}] "
+                             f"tensor, got {tuple(w.shape)} {w.dtype}")
+        K, ncols = w.shape
+        N = ncols // 2 if glu else ncols
+        cb, sb = weight_quant_bytes(WEIGHT_FORMATS[fmt], K, N, glu)
+        codes = torch.empty(cb, dtype=torch.uint8, device=w.device)
+        scales = None
+        if sb:
+            scales = torch.empty((ncols,) if fmt == "fp8" else (K // 32, ncols), dtype=torch.float32, device=w.device)
+        st = stream_ptr(w.device) if stream is None else stream
+        check(lib().mt_weight_quant(WEIGHT_FORMATS[fmt], w.data_ptr(), ncols, K, N, int(bool(glu)), codes.data_ptr(),
+                                    None if scales is None else scales.data_ptr(), st), "mt_weight_quant")
+        return cls(fmt, K, N, bool(glu), codes, scales)
+
+    def dequantize(self, out=None, codes_out=None, stream: Optional[int] = None):
+        """The dequantised weight W' as a float32 [K, ncols] device tensor (mt_weight_dequant), into
+        `out` when given (any dense float32 buffer of at least K ncols elements: its head is
+        written and returned as a view). codes_out: a dense [K, ncols] uint16 (bf16) / uint8 (fp8)
+        / int8 (int4) tensor that receives the codes."""
+        torch = _torch()
+        n = self.K * self.ncols
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=self.codes.device)
+        if out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda or out.numel() < n:
+            raise ValueError(f"dequantize: out must be a dense device float32 buffer of >= {n} elements")
+        want = {"bf16": torch.uint16, "fp8": torch.uint8, "int4": torch.int8}[self.fmt]
+        if codes_out is not None and (codes_out.dtype != want or tuple(codes_out.shape) != (self.K, self.ncols)
+                                      or not codes_out.is_contiguous() or not codes_out.is_cuda):
+            raise ValueError(f"dequantize: codes_out must be a dense device {want} [{self.K}, {self.ncols}] tensor")
+        st = stream_ptr(out.device) if stream is None else stream
+        check(lib().mt_weight_dequant(WEIGHT_FORMATS[self.fmt], self.codes.data_ptr(),
+                                      None if self.scales is None else self.scales.data_ptr(), self.K, self.N,
+                                      int(self.glu), out.data_ptr(), None if codes_out is None else codes_out.data_ptr(),
+                                      st), "mt_weight_dequant")
+        return out.view(-1)[:n].view(self.K, self.ncols)
+
+
 fused_linear_calls = 0  # launches of mt_linear_rows through fused_linear (tests tell the path by it)
 
 
@@ -1087,11 +1169,17 @@ def fused_linear(x, weights, biases=None, residuals=None, gamma=None, beta=None,
     after the bias). glu: the same for the gate: such a group's weight is [K, 2 N_g] (gate
     columns, then up columns), its bias [2 N_g], and out_g [M, N_g] = silu(gate) * up (+ residual).
     Ungated weights are [K, N_g], biases [N_g]; residuals and outs are dense [M, N_g]. outs:
-    tensors to write into (allocated when None). Returns the list of outputs. Inference only."""
+    tensors to write into (allocated when None). Returns the list of outputs. Inference only.
+    QuantizedWeights in place of the weight tensors (all of one format, each packed with its
+    group's glu) run mt_linear_rows_wq: the same call on the weights' storage."""
     global fused_linear_calls
     torch = _torch()
     G = len(weights)
-    _check_dev(x, *weights)
+    quant = [isinstance(w, QuantizedWeight) for w in weights]
+    if any(quant) and (not all(quant) or len({w.fmt for w in weights}) != 1):
+        raise ValueError("fused_linear: the weights of a call are all fp32 tensors or QuantizedWeights of one format")
+    quant = all(quant) and G > 0
+    _check_dev(x, *([w.codes for w in weights] if quant else weights))
     if x.dim() != 2 or x.dtype != torch.float32 or (x.stride(1) != 1 and x.shape[1] != 1):
         raise ValueError(f"fused_linear takes a float32 [M, K] x with unit-stride rows, got {tuple(x.shape)} {x.dtype}")
     M, K = x.shape
@@ -1120,12 +1208,19 @@ def fused_linear(x, weights, biases=None, residuals=None, gamma=None, beta=None,
     outs = [None] * G if outs is None else list(outs)
     ns = []
     for g, w in enumerate(weights):
-        if w.dim() != 2 or w.shape[0] != K or w.dtype != torch.float32 or not w.is_contiguous() or (glu[g] and w.shape[1] % 2):
+        if quant:
+            if w.K != K or w.glu != glu[g]:
+                raise ValueError(f"fused_linear: weight {g} was packed for K = {w.K}, glu = {w.glu}; the call has "
+                                 f"K = {K}, glu = {glu[g]}")
+            ncols = w.ncols
+        elif w.dim() != 2 or w.shape[0] != K or w.dtype != torch.float32 or not w.is_contiguous() or (glu[g] and w.shape[1] % 2):
             raise ValueError(f"fused_linear: weight {g} must be a dense float32 [{K}, {'2 N' if glu[g] else 'N'}] tensor, "
                              f"got {tuple(w.shape)}")
-        n = w.shape[1] // 2 if glu[g] else w.shape[1]
+        else:
+            ncols = w.shape[1]
+        n = ncols // 2 if glu[g] else ncols
         ns.append(n)
-        for name, t, shape in (("bias", biases[g], (w.shape[1],)), ("residual", residuals[g], (M, n)), ("out", outs[g], (M, n))):
+        for name, t, shape in (("bias", biases[g], (ncols,)), ("residual", residuals[g], (M, n)), ("out", outs[g], (M, n))):
             if t is None:
                 continue
             if t.dtype != torch.float32 or t.numel() != shape[0] * (shape[1] if len(shape) > 1 else 1) or not t.is_contiguous() or not t.is_cuda:
@@ -1136,15 +1231,21 @@ def fused_linear(x, weights, biases=None, residuals=None, gamma=None, beta=None,
     mask = lambda v: sum(1 << g for g in range(G) if v[g])  # noqa: E731
     st = stream_ptr(x.device) if stream is None else stream
     head = (G, x.data_ptr(), x.stride(0) if M > 1 else K, M, K)
-    tail = (ptrs(weights), (ctypes.c_int64 * G)(*ns), ptrs(biases), ptrs(residuals), ptrs(outs), mask(gelu))
+    tail = ((ctypes.c_int64 * G)(*ns), ptrs(biases), ptrs(residuals), ptrs(outs), mask(gelu))
     gp, bp = None if gamma is None else gamma.data_ptr(), None if beta is None else beta.data_ptr()
-    if norm != "rms" and eps is None and not any(glu):
-        check(lib().mt_linear_rows(*head, gp, bp, *tail, st), "mt_linear_rows")
+    mode = 2 if norm == "rms" else (0 if gamma is None else 1)
+    if not quant and norm != "rms" and eps is None and not any(glu):
+        check(lib().mt_linear_rows(*head, gp, bp, ptrs(weights), *tail, st), "mt_linear_rows")
     else:
-        mode = 2 if norm == "rms" else (0 if gamma is None else 1)
         if eps is None:
             eps = 1e-5 if mode == 2 else 1e-8
-        check(lib().mt_linear_rows_ex(*head, mode, gp, bp, float(eps), *tail, mask(glu), st), "mt_linear_rows_ex")
+        if quant:
+            check(lib().mt_linear_rows_wq(WEIGHT_FORMATS[weights[0].fmt], *head, mode, gp, bp, float(eps),
+                                          ptrs([w.codes for w in weights]), ptrs([w.scales for w in weights]), *tail,
+                                          mask(glu), st), "mt_linear_rows_wq")
+        else:
+            check(lib().mt_linear_rows_ex(*head, mode, gp, bp, float(eps), ptrs(weights), *tail, mask(glu), st),
+                  "mt_linear_rows_ex")
     fused_linear_calls += 1
     return outs
 

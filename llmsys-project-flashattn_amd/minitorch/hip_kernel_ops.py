@@ -756,7 +756,9 @@ class HipKernelOps(TensorOps):
         group = lambda ts: None if ts is None else [dense(t) for t in ts]  # noqa: E731
         xv = _torch_view(x if x._tensor.strides[-1] == 1 else x.contiguous())
         beta = None if ln is None or len(ln) < 2 or ln[1] is None else dense(ln[1]).reshape(-1)
-        outs = _hip.fused_linear(xv, [dense(w) for w in weights], group(biases), group(residuals),
+        # a QuantizedWeight (a model after quantize_weights) goes through as it is
+        outs = _hip.fused_linear(xv, [w if isinstance(w, _hip.QuantizedWeight) else dense(w) for w in weights],
+                                 group(biases), group(residuals),
                                  gamma=None if ln is None else dense(ln[0]).reshape(-1),
                                  beta=beta, gelu=gelu, norm=norm, eps=eps, glu=glu)
         return [_wrap(o.reshape(-1), o.shape, x.backend) for o in outs]

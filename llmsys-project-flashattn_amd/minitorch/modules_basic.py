@@ -61,9 +61,32 @@ class Linear(Module):
             self.bias = Parameter(tensor_from_numpy(
                 np.random.uniform(-bound, bound, (out_size,)), backend=backend, requires_grad=True))
 
+    def quantize(self, fmt: str, glu: bool, scratch) -> None:
+        """DecoderLM.quantize_weights: the weight becomes a QuantizedWeight (qweight) and the fp32
+        parameter is released. scratch: a float32 device buffer of at least in_size x out_size
+        elements, shared by the model's linears, that forward dequantises into."""
+        from ._hip import QuantizedWeight
+        self.qweight = QuantizedWeight.from_tensor(self.weights.value, fmt, glu)
+        self.qscratch = scratch
+        del self.__dict__["_parameters"]["weights"]
+
+    def weight(self):
+        """What the fused skinny linear takes: the fp32 weight, or the QuantizedWeight."""
+        return self.weights.value if self.qweight is None else self.qweight
+
+    def dense_weight(self, backend):
+        """The fp32 [in_size, out_size] weight for a matmul: the parameter, or (the same quantised
+        model on the unfused path) W' dequantised into the scratch, valid until the next
+        quantised linear's call."""
+        if self.qweight is None:
+            return self.weights.value
+        from .hip_kernel_ops import _wrap
+        wq = self.qweight.dequantize(out=self.qscratch)
+        return _wrap(wq.reshape(-1), wq.shape, backend)
+
     def forward(self, x: Tensor) -> Tensor:
         batch, in_size = x.shape
-        out = x @ self.weights.value
+        out = x @ self.dense_weight(x.backend)
         if self.bias is not None:
             out = out + self.bias.value
         return out

@@ -253,14 +253,14 @@ class MultiHeadAttention(Module):
         Returns [B T, n_embd]: attention(ln(flat)) + flat."""
         proj = (self.q_projection, self.k_projection, self.v_projection)
         biases = [_bias(p) for p in proj]
-        q, k, v = flat.fused_linear([p.weights.value for p in proj], None if biases[0] is None else biases,
+        q, k, v = flat.fused_linear([p.weight() for p in proj], None if biases[0] is None else biases,
                                     **_norm_kw(ln))
         shp = (batch_size, seq_len, self.n_head, self.attn_hidden_dim)
         kv_shp = (batch_size, seq_len, self.n_kv_head, self.attn_hidden_dim)
         q, k, v = q.view(*shp).permute(0, 2, 1, 3), k.view(*kv_shp).permute(0, 2, 1, 3), v.view(*kv_shp).permute(0, 2, 1, 3)
         attn = self._cached_attention(q, k, v, kv_len, cache)
         return attn.view(batch_size * seq_len, self.n_embd).fused_linear(
-            self.out_projection.weights.value, _bias(self.out_projection), residual=flat)
+            self.out_projection.weight(), _bias(self.out_projection), residual=flat)
 
     def _cached_attention(self, q, k, v, kv_len, cache):
         from .kv_cache import KVCache
@@ -394,7 +394,7 @@ class FeedForward(Module):
                 and x._tensor.on_device):
             # linear_in's bias add and the GELU as one kernel each way (BiasGelu)
             from .tensor_functions import BiasGelu
-            h = BiasGelu.apply(flat @ self.linear_in.weights.value, self.linear_in.bias.value)
+            h = BiasGelu.apply(flat @ self.linear_in.dense_weight(be), self.linear_in.bias.value)
         else:
             h = GELU(self.linear_in(flat))
         return self.dropout(self.linear_out(h)).view(batch_size, seq_len, n_embd)
@@ -406,8 +406,8 @@ class FeedForward(Module):
         bias and the GELU (or the gate) in one launch, linear_out its bias and the residual flat in another. Returns
         [rows, n_embd]: ff(ln(flat)) + flat (no dropout: the caller checked)."""
         glu = self.activation == "swiglu"  # the gate and the up half in the one launch
-        h = flat.fused_linear(self.linear_in.weights.value, _bias(self.linear_in), gelu=not glu, glu=glu, **_norm_kw(ln))
-        return h.fused_linear(self.linear_out.weights.value, _bias(self.linear_out), residual=flat)
+        h = flat.fused_linear(self.linear_in.weight(), _bias(self.linear_in), gelu=not glu, glu=glu, **_norm_kw(ln))
+        return h.fused_linear(self.linear_out.weight(), _bias(self.linear_out), residual=flat)
 
 
 class TransformerLayer(Module):
@@ -525,6 +525,65 @@ class DecoderLM(Module):
         self.ln = _make_norm(norm, n_embd, ln_eps, backend, use_fused_kernel)
         self.graph_captures = 0  # hipGraph captures of the decode step (generate(graph=True))
         self.spec_stats = None   # the last generate(speculate=...) call's counters
+        self.quantized = None    # the format quantize_weights stored the linears' weights in
+
+    def _linears(self):
+        """(name, Linear, gated) of every linear quantize_weights stores: each block's Q / K / V
+        and output projections, linear_in (gated in a swiglu block) and linear_out, and lm_head."""
+        out = []
+        for i in range(self.n_layer):
+            layer = getattr(self, f"t_layer_{i + 1}")
+            for name in ("q_projection", "k_projection", "v_projection", "out_projection"):
+                out.append((f"t_layer_{i + 1}.attention.{name}", getattr(layer.attention, name), False))
+            out.append((f"t_layer_{i + 1}.ff.linear_in", layer.ff.linear_in, layer.ff.activation == "swiglu"))
+            out.append((f"t_layer_{i + 1}.ff.linear_out", layer.ff.linear_out, False))
+        out.append(("lm_head", self.lm_head, False))
+        return out
+
+    @property
+    def weight_nbytes(self) -> int:
+        """Device bytes of the linears' weights as they are stored now (fp32, or codes and scales)."""
+        return sum(4 * lin.weights.value.size if lin.qweight is None else lin.qweight.nbytes
+                   for _, lin, _ in self._linears())
+
+    def quantize_weights(self, fmt: str) -> None:
+        """Weight-only quantisation, in place and for good: every block's linears and lm_head are
+        stored as fmt ("bf16", "fp8": e4m3 with a scale per column, or "int4": a scale per column
+        and 32 input rows; QuantizedWeight) and their fp32 parameters released; weight_nbytes
+        tells the bytes before and after. Embeddings, norms and biases stay fp32. Needs
+        fused_step=True: a cached step of at most 64 rows multiplies the stored codes directly
+        (mt_linear_rows_wq), and every other forward (the prefill, larger steps, no cache)
+        dequantises each weight into one scratch buffer, allocated here for the largest linear,
+        and runs the fp32 matmul on it: the same quantised model on every path, so generate gives
+        the same ids eager, with graph=True and with speculate, on any cache kind. Every linear's
+        input width must be a multiple of 128 (at most 1024). The model is left in eval() and
+        can no longer be trained. Unset, nothing changes."""
+        import torch
+        from . import _hip
+        if not self.fused_step:
+            raise ValueError("quantize_weights needs a model built with fused_step=True (the cached step runs the "
+                             "quantised skinny linear)")
+        if self.quantized is not None:
+            raise ValueError(f"the weights are already stored as {self.quantized}")
+        if fmt not in _hip.WEIGHT_FORMATS:
+            raise ValueError(f'fmt must be "bf16", "fp8" or "int4", got {fmt!r}')
+        linears = self._linears()
+        for name, lin, _ in linears:
+            width = lin.weights.value.shape[0]
+            if width % 128 or width > FUSED_STEP_MAX_WIDTH:
+                raise ValueError(f"quantize_weights: {name} has an input width of {width}; the quantised kernel takes "
+                                 f"multiples of 128 up to {FUSED_STEP_MAX_WIDTH}")
+        scratch = torch.empty(max(lin.weights.value.size for _, lin, _ in linears), dtype=torch.float32, device="cuda")
+        for _, lin, glu in linears:
+            lin.quantize(fmt, glu, scratch)
+        self.drop_decode_graphs()  # captured over the released weights
+        self.eval()
+        self.quantized = fmt
+
+    def train(self) -> None:
+        if self.quantized is not None:
+            raise RuntimeError(f"the weights are stored as {self.quantized} (quantize_weights): the model cannot be trained")
+        super().train()
 
     def forward(self, idx, kv_len=None, cache=None):
         """kv_len: optional valid-token count per batch row of a right-padded batch (keys past
@@ -554,7 +613,7 @@ class DecoderLM(Module):
         """The final LayerNorm and lm_head over flat [rows, n_embd]; for a decode or extend step
         (step=True) of a fused_step model within the fused kernel's range, one launch."""
         if step and _takes_fused_step(self, flat.shape[0], self.n_embd, flat.backend, self.p_dropout):
-            return flat.fused_linear(self.lm_head.weights.value, _bias(self.lm_head), **_norm_kw(self.ln))
+            return flat.fused_linear(self.lm_head.weight(), _bias(self.lm_head), **_norm_kw(self.ln))
         return self.lm_head(self.ln(flat))
 
     def new_cache(self, batch_size: int, kv_dtype=None, page_size=None, n_pages=None):

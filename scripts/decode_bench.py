@@ -113,6 +113,14 @@ PagedKVCaches holding a ragged batch of one row of 4096 tokens and seven of 64.
                 rotary model over a 97-token vocabulary, whose greedy continuation falls into cycles, and
                 random prompts over 10000 tokens (next to nothing is accepted: the overhead)
 
+--wq-legs instead writes profiles/wq_linear_bench.json (weight-only quantised linear):
+
+  kernel       mt_linear_rows_wq per format (bf16, fp8, int4) against mt_linear_rows on the dequantised fp32
+                weights, LayerNorm + bias, at 1, 8 and 64 rows on (K, N) = (256, 256) and (256, 10000), as
+                captured graphs, alternated
+  generate     generate(graph=True) tokens/s of the quantize_weights model per format against the fp32
+                fused_step model, batch 1 and 8
+
 No gate: what is measured is recorded.
 """
 import argparse
@@ -1316,8 +1324,89 @@ def fused_legs(args, torch, minitorch, _hip):
         json.dump(res, f, indent=1)
 
 
+WQ_FORMATS = ("bf16", "fp8", "int4")
+
+
+def bench_wq_kernel(torch, _hip, M, K, N, rounds, warmup, inner=32):
+    """mt_linear_rows_wq per storage format against mt_linear_rows on the dequantised fp32 weights W'
+    (the same values, 4 bytes each), LayerNorm + bias, every leg `inner` calls replayed from one
+    captured graph and the legs alternated. Warm: the weights stay in cache between calls."""
+    rng = np.random.default_rng(0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()  # noqa: E731
+    x, gamma, beta = t(rng.normal(0.5, 1, (M, K))), t(1 + 0.3 * rng.standard_normal(K)), t(0.2 * rng.standard_normal(K))
+    W, b = t(rng.uniform(-K ** -0.5, K ** -0.5, (K, N))), t(rng.uniform(-K ** -0.5, K ** -0.5, N))
+    out = torch.empty((M, N), device="cuda")
+    run = lambda w: _hip.fused_linear(x, [w], [b], gamma=gamma, beta=beta, outs=[out])  # noqa: E731
+    legs, nbytes = {}, {}
+    for fmt in WQ_FORMATS:
+        q = _hip.QuantizedWeight.from_tensor(W, fmt)
+        wd = q.dequantize()
+        nbytes[fmt] = q.nbytes
+        legs[f"{fmt}_wq"] = _graph_of(torch, lambda i, w=q: run(w), inner)
+        legs[f"{fmt}_fp32"] = _graph_of(torch, lambda i, w=wd: run(w), inner)
+    res = {"M": M, "K": K, "N": N, "rounds": rounds, "calls_per_replay": inner, "fp32_W_bytes": 4 * K * N,
+           "stored_bytes": nbytes, **_alternate(torch, legs, rounds, warmup, inner)}
+    for fmt in WQ_FORMATS:
+        res[f"{fmt}_fp32_over_wq"] = res[f"{fmt}_fp32_s_median"] / res[f"{fmt}_wq_s_median"]
+    return res
+
+
+def bench_generate_wq(torch, minitorch, n_positions, prompt_len, new_tokens, batch, rounds):
+    """generate(graph=True) tokens/s of the fused_step model with its weights stored per format
+    against the same model in fp32, alternated in one process."""
+    backend = minitorch.TensorBackend(minitorch.HipKernelOps)
+    rng = np.random.default_rng(0)
+    prompts = [[int(t) for t in rng.integers(0, 10000, prompt_len)] for _ in range(batch)]
+    lms = {}
+    for name in ("fp32",) + WQ_FORMATS:
+        np.random.seed(0)  # the same weights
+        lms[name] = minitorch.DecoderLM(n_vocab=10000, n_embd=256, n_head=8, n_positions=n_positions, p_dropout=0.0,
+                                        backend=backend, use_fused_kernel=True, use_flash_attention=True, fused_step=True)
+        if name != "fp32":
+            lms[name].quantize_weights(name)
+    legs = {}
+    for name, lm in lms.items():
+        legs[f"{name}_one"] = lambda lm=lm: lm.generate(prompts[:1], new_tokens, graph=True)
+        legs[f"{name}_batch"] = lambda lm=lm: lm.generate(prompts, new_tokens, graph=True)
+    for fn in legs.values():  # warm-up: captures the graphs
+        fn()
+    rate = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            toks = fn()
+            rate[k].append(sum(len(t) for t in toks) / (time.perf_counter() - t0))
+    med = {k: statistics.median(v) for k, v in rate.items()}
+    return {"n_positions": n_positions, "prompt_len": prompt_len, "new_tokens": new_tokens, "batch": batch,
+            "rounds": rounds, "weight_nbytes": {name: lm.weight_nbytes for name, lm in lms.items()},
+            **{f"{k}_tokens_per_s_median": v for k, v in med.items()},
+            **{f"{k}_tokens_per_s_best": max(v) for k, v in rate.items()},
+            **{f"{fmt}_over_fp32_{k}": med[f"{fmt}_{k}"] / med[f"fp32_{k}"] for fmt in WQ_FORMATS for k in ("one", "batch")}}
+
+
+def wq_legs(args, torch, minitorch, _hip):
+    res = {"device": torch.cuda.get_device_name(0), "kernel": [], "generate": []}
+    for K, N in ((256, 256), (256, 10000)):  # config 5's linears, and its lm_head
+        for M in (1, 8, 64):
+            r = bench_wq_kernel(torch, _hip, M, K, N, args.rounds, args.warmup)
+            print(json.dumps(r), flush=True)
+            res["kernel"].append(r)
+    if not args.skip_generate:
+        for npos, plen, new, batch, rounds in ((40, 8, 32, 8, 5), (1024, 768, 128, 8, 3)):
+            r = bench_generate_wq(torch, minitorch, npos, plen, new, batch, rounds)
+            print(json.dumps(r), flush=True)
+            res["generate"].append(r)
+    os.makedirs(os.path.dirname(args.wq_out), exist_ok=True)
+    with open(args.wq_out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--wq-legs", action="store_true",
+                    help="the weight-only quantised skinny linear per format against the fp32 kernel on the same "
+                         "values, and generate(graph=True) of a quantize_weights model against the fp32 model")
+    ap.add_argument("--wq-out", default=os.path.join(ROOT, "profiles", "wq_linear_bench.json"))
     ap.add_argument("--spec-legs", action="store_true",
                     help="run the speculative-decoding legs instead, into --spec-out")
     ap.add_argument("--spec-out", default=os.path.join(ROOT, "profiles", "spec_bench.json"))
@@ -1364,6 +1453,8 @@ def main():
     from minitorch import _hip
     if args.lib:
         _hip.use_library(os.path.abspath(args.lib), allow_missing=True)
+    if args.wq_legs:
+        return wq_legs(args, torch, minitorch, _hip)
     if args.fused_legs:
         return fused_legs(args, torch, minitorch, _hip)
     if args.llama_legs:
