@@ -603,6 +603,49 @@ int mt_linear_rows_wq(int fmt, int G, const float* x, int64_t ldx, int64_t M, in
                       const float* const* residual, float* const* out, int gelu_mask, int glu_mask,
                       void* stream);
 
+/* ---- mixture-of-experts MLP of the cached decode step (fp32, device pointers) ----
+ * A router picks k of E gated expert MLPs per row and only the chosen experts' weights are read:
+ *   xh = norm(x) [M, K], norm / gamma / beta / eps as mt_linear_rows_ex (0 none, 1 LayerNorm,
+ *        2 RMSNorm; the same sums, so the same bits);
+ *   r = xh @ Wr, Wr [K, E] without bias, fp32;
+ *   the k largest of r[m, :], the lower index first among equals, ordered by descending logit and
+ *   then index: slots j = 0..k-1 with expert e(m,j); gates are the softmax over the chosen logits,
+ *   g(m,j) = exp(r_j - r_0) / sum_j' exp(r_j' - r_0), summed in ascending slot order;
+ *   expert e: h = silu(xh W_gate + b_gate) * (xh W_up + b_up) with W_in[e] [K, 2F] (F gate columns,
+ *   then F up columns; silu as mt_swiglu_fw), y_e = h W_out[e] + b_out[e], W_out[e] [F, N];
+ *   out[m] = residual[m] + (((g0 y_e0) + g1 y_e1) + ...), ascending slots.
+ * Stacked weights: W_in [E, K, 2F], b_in [E, 2F] or NULL, W_out [E, F, N], b_out [E, N] or NULL;
+ * residual [M, N] dense or NULL, out [M, N] dense. 1 <= M <= 64; K a multiple of 4 in 4..1024;
+ * 1 <= F, N <= 2^20; 2 <= E <= 64; 1 <= k <= min(E, 8). x (rows ldx >= K apart, ldx % 4 == 0),
+ * gamma, beta and the workspace are 16-byte aligned, everything else 4-byte aligned (weights take
+ * 16-byte loads where F resp. N % 4 == 0 and the pointer allows; the values do not depend on it).
+ * A row with a non-finite router logit gets a NaN output row, topk_idx -1 and NaN gates; no other
+ * row is touched by it. An expert's weights meet only the rows routed to it (there is no
+ * multiplication by a zero gate): inf or NaN in an expert nobody chose changes nothing.
+ * mt_moe_rows: four launches (route; expert-in over (expert, 32 gated columns); expert-out over
+ *   (expert, 64 columns), both on the fp32 MFMA with K split over four waves when the reduction
+ *   length is a multiple of 16; the slot sum). A workgroup whose expert no row chose leaves before
+ *   reading its weights. Grids depend on the sizes alone; no atomics; nothing is allocated (the
+ *   workspace of mt_moe_rows_workspace_bytes is the caller's and may be reused by the next call
+ *   on the stream); stream-ordered, capturable. The bits of out row m are a function of x row m,
+ *   residual row m, the weights and the sizes: not of M or of the rows sharing its experts.
+ *   topk_idx [M, k] int32 and topk_gate [M, k] fp32: optional outputs (NULL to skip).
+ * mt_moe_route: the routing stage alone, for any M >= 1: optional outputs xh [M, K] dense
+ *   (16-byte aligned), topk_idx, topk_gate and mask [M, E] (1.0 for a chosen expert, else 0.0);
+ *   at least one is not NULL.
+ * Refused with a status and a mt_last_error() message before any device call: a size out of
+ * range, k > E, a NULL or misaligned pointer, a workspace that is too small, out overlapping x,
+ * and the norm arguments mt_linear_rows_ex refuses. */
+int mt_moe_rows_workspace_bytes(int64_t M, int64_t K, int64_t F, int64_t N, int64_t E, int64_t k, int64_t* bytes);
+int mt_moe_route(const float* x, int64_t ldx, int64_t M, int64_t K, int norm, const float* gamma,
+                 const float* beta, float eps, const float* Wr, int64_t E, int64_t k, float* xh,
+                 int32_t* topk_idx, float* topk_gate, float* mask, void* stream);
+int mt_moe_rows(const float* x, int64_t ldx, int64_t M, int64_t K, int norm, const float* gamma,
+                const float* beta, float eps, const float* Wr, int64_t E, int64_t k, const float* W_in,
+                const float* b_in, int64_t F, const float* W_out, const float* b_out, int64_t N,
+                const float* residual, float* out, int32_t* topk_idx, float* topk_gate, void* workspace,
+                int64_t workspace_bytes, void* stream);
+
 /* ---- RMSNorm and SwiGLU (a Llama-shaped block's training path), device pointers (fp32) ----
  * RMSNorm over the last dim of [rows, hidden]: rstd[r] = 1 / sqrt(mean_j x[r,j]^2 + eps),
  * out = gamma (x rstd). Backward, with g = gamma dy: dx = rstd g - x rstd^3 (sum_j g_j x_j) / hidden,

@@ -117,6 +117,11 @@ _PROTOS = {
     "mt_weight_dequant": (_int, [_int, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp]),
     "mt_linear_rows_wq": (_int, [_int, _int, _vp, _i64, _i64, _i64, _int, _vp, _vp, ctypes.c_float, _vpp, _vpp, _i64p,
                                  _vpp, _vpp, _vpp, _int, _int, _vp]),
+    "mt_moe_rows_workspace_bytes": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _i64p]),
+    "mt_moe_route": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _vp, ctypes.c_float, _vp, _i64, _i64, _vp, _vp, _vp, _vp,
+                            _vp]),
+    "mt_moe_rows": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _vp, ctypes.c_float, _vp, _i64, _i64, _vp, _vp, _i64,
+                           _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "mt_rmsnorm_fw": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_float, _vp]),
     "mt_rmsnorm_bw_workspace_bytes": (_i64, [_i64, _i64]),
     "mt_rmsnorm_bw": (_int, [_vp] * 6 + [_i64, _i64, _vp, _vp]),
@@ -1248,6 +1253,120 @@ def fused_linear(x, weights, biases=None, residuals=None, gamma=None, beta=None,
                   "mt_linear_rows_ex")
     fused_linear_calls += 1
     return outs
+
+
+moe_rows_calls = 0  # launches of mt_moe_rows through moe_rows (tests tell the path by it)
+
+
+def _moe_norm(fn, x, gamma, beta, norm, eps):
+    """(mode, gamma ptr, beta ptr, eps) of a mixture-of-experts call: fused_linear's norm rules."""
+    torch = _torch()
+    if x.dim() != 2 or x.dtype != torch.float32 or (x.stride(1) != 1 and x.shape[1] != 1):
+        raise ValueError(f"{fn} takes a float32 [M, K] x with unit-stride rows, got {tuple(x.shape)} {x.dtype}")
+    if norm not in (None, "layer", "rms"):
+        raise ValueError(f'{fn}: norm must be None, "layer" or "rms", got {norm!r}')
+    if norm == "rms":
+        if gamma is None or beta is not None:
+            raise ValueError(f'{fn}: norm="rms" takes gamma and no beta')
+    elif (gamma is None) != (beta is None):
+        raise ValueError(f"{fn}: gamma and beta go together")
+    elif norm == "layer" and gamma is None:
+        raise ValueError(f'{fn}: norm="layer" needs gamma and beta')
+    K = x.shape[1]
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != K or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError(f"{fn}: {name} must be a dense device float32 [{K}] tensor")
+    mode = 2 if norm == "rms" else (0 if gamma is None else 1)
+    if eps is None:
+        eps = 1e-5 if mode == 2 else 1e-8
+    return mode, None if gamma is None else gamma.data_ptr(), None if beta is None else beta.data_ptr(), float(eps)
+
+
+def _moe_dense(fn, name, t, shape):
+    torch = _torch()
+    if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or not t.is_cuda):
+        raise ValueError(f"{fn}: {name} must be a dense device float32 {list(shape)} tensor")
+    return None if t is None else t.data_ptr()
+
+
+def moe_rows_workspace_bytes(M: int, K: int, F: int, N: int, E: int, k: int) -> int:
+    """Bytes of the workspace mt_moe_rows needs for these sizes (mt_moe_rows_workspace_bytes)."""
+    b = ctypes.c_int64(0)
+    if lib().mt_moe_rows_workspace_bytes(M, K, F, N, E, k, ctypes.byref(b)) != 0:
+        raise ValueError(lib().mt_last_error().decode(errors="replace"))
+    return b.value
+
+
+def moe_route(x, router, top_k, gamma=None, beta=None, norm=None, eps=None, want=("idx", "gate"),
+              stream: Optional[int] = None):
+    """The routing stage of the mixture-of-experts MLP alone (mt_moe_route): norm(x) [M, K] (any
+    M), the logits norm(x) @ router [K, E], the top_k largest per row (lower index first among
+    equals) and their softmax gates. want: which of "xh" [M, K], "idx" [M, top_k] int32, "gate"
+    [M, top_k], "mask" [M, E] (1.0 at the chosen experts) to compute; returns them as a dict. A row
+    with a non-finite logit has idx -1, NaN gates and a zero mask row. norm / gamma / beta / eps as
+    fused_linear."""
+    torch = _torch()
+    _check_dev(x, router)
+    mode, gp, bp, eps = _moe_norm("moe_route", x, gamma, beta, norm, eps)
+    M, K = x.shape
+    if router.dim() != 2 or router.shape[0] != K:
+        raise ValueError(f"moe_route: router must be [{K}, E], got {tuple(router.shape)}")
+    E = router.shape[1]
+    _moe_dense("moe_route", "router", router, (K, E))
+    shapes = {"xh": ((M, K), torch.float32), "idx": ((M, top_k), torch.int32), "gate": ((M, top_k), torch.float32),
+              "mask": ((M, E), torch.float32)}
+    out = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=x.device) for name in want}
+    ptr = lambda name: out[name].data_ptr() if name in out else None  # noqa: E731
+    st = stream_ptr(x.device) if stream is None else stream
+    check(lib().mt_moe_route(x.data_ptr(), x.stride(0) if M > 1 else K, M, K, mode, gp, bp, eps, router.data_ptr(), E,
+                             int(top_k), ptr("xh"), ptr("idx"), ptr("gate"), ptr("mask"), st), "mt_moe_route")
+    return out
+
+
+def moe_rows(x, router, w_in, w_out, b_in=None, b_out=None, top_k=2, residual=None, gamma=None, beta=None,
+             norm=None, eps=None, out=None, workspace=None, topk_idx=None, topk_gate=None,
+             stream: Optional[int] = None):
+    """The mixture-of-experts MLP of a cached step (mt_moe_rows; fp32): out [M, N] = residual +
+    sum_j gate_j expert_{e_j}(norm(x)) over the top_k experts the router [K, E] picks per row of x
+    [M <= 64, K]; expert e is silu(xh w_in[e][:, :F] + b) * (xh w_in[e][:, F:] + b) @ w_out[e] + b
+    with w_in [E, K, 2F], b_in [E, 2F], w_out [E, F, N], b_out [E, N] (biases and residual [M, N]
+    optional). norm / gamma / beta / eps as fused_linear. workspace: a uint8 device buffer of at
+    least moe_rows_workspace_bytes(...) bytes, owned by the caller and reusable by the next call
+    on the stream (None: allocated here). topk_idx [M, top_k] int32 / topk_gate [M, top_k]:
+    optional tensors that receive the routing. Returns out. Inference only."""
+    global moe_rows_calls
+    torch = _torch()
+    _check_dev(x, router, w_in, w_out)
+    mode, gp, bp, eps = _moe_norm("moe_rows", x, gamma, beta, norm, eps)
+    M, K = x.shape
+    if router.dim() != 2 or w_in.dim() != 3 or w_out.dim() != 3 or w_in.shape[2] % 2:
+        raise ValueError(f"moe_rows takes router [K, E], w_in [E, K, 2F] and w_out [E, F, N], got "
+                         f"{tuple(router.shape)}, {tuple(w_in.shape)}, {tuple(w_out.shape)}")
+    E, F, N = router.shape[1], w_in.shape[2] // 2, w_out.shape[2]
+    top_k = int(top_k)
+    fn = "moe_rows"
+    args = [_moe_dense(fn, *a) for a in (("router", router, (K, E)), ("w_in", w_in, (E, K, 2 * F)),
+                                          ("b_in", b_in, (E, 2 * F)), ("w_out", w_out, (E, F, N)),
+                                          ("b_out", b_out, (E, N)), ("residual", residual, (M, N)))]
+    need = moe_rows_workspace_bytes(M, K, F, N, E, top_k)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    elif workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"moe_rows: workspace must be a dense device uint8 buffer of >= {need} bytes")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    _moe_dense(fn, "out", out, (M, N))
+    for name, t, dt in (("topk_idx", topk_idx, torch.int32), ("topk_gate", topk_gate, torch.float32)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (M, top_k) or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError(f"moe_rows: {name} must be a dense device {dt} [{M}, {top_k}] tensor")
+    st = stream_ptr(x.device) if stream is None else stream
+    check(lib().mt_moe_rows(x.data_ptr(), x.stride(0) if M > 1 else K, M, K, mode, gp, bp, eps, args[0], E, top_k,
+                            args[1], args[2], F, args[3], args[4], N, args[5], out.data_ptr(),
+                            None if topk_idx is None else topk_idx.data_ptr(),
+                            None if topk_gate is None else topk_gate.data_ptr(), workspace.data_ptr(),
+                            workspace.numel(), st), "mt_moe_rows")
+    moe_rows_calls += 1
+    return out
 
 
 def scratch_bytes() -> int:

@@ -762,3 +762,38 @@ class HipKernelOps(TensorOps):
                                  gamma=None if ln is None else dense(ln[0]).reshape(-1),
                                  beta=beta, gelu=gelu, norm=norm, eps=eps, glu=glu)
         return [_wrap(o.reshape(-1), o.shape, x.backend) for o in outs]
+
+    @staticmethod
+    def moe_workspace(like: Tensor, M: int, K: int, F: int, N: int, E: int, top_k: int):
+        """A workspace for moe_mlp calls of up to M rows at these sizes (its bytes grow with M), on
+        like's device: a uint8 torch buffer the caller owns and keeps for as long as anything, a
+        captured graph included, may still run on it."""
+        import torch
+        return torch.empty(_hip.moe_rows_workspace_bytes(M, K, F, N, E, int(top_k)), dtype=torch.uint8,
+                           device=_torch_view(like).device)
+
+    @staticmethod
+    def moe_mlp(x: Tensor, router, w_in, w_out, b_in=None, b_out=None, top_k=2, residual=None, norm=None, eps=None,
+                ln=None, workspace=None):
+        """The mixture-of-experts MLP of a cached decode step (mt_moe_rows): x [M <= 64, K] through
+        the top_k experts the router [K, E] picks per row; w_in [E, K, 2F] (gate columns, then up
+        columns), w_out [E, F, N], optional b_in [E, 2F], b_out [E, N] and residual [M, N]; ln /
+        norm / eps as fused_linear. workspace: the caller's buffer (moe_workspace; it must outlive every
+        captured graph that recorded a call on it), or None for one allocated for this call.
+        Returns a new [M, N] tensor (no history: inference only)."""
+        dense = lambda t: None if t is None else _torch_view(_dense(t))  # noqa: E731
+        xv = _torch_view(x if x._tensor.strides[-1] == 1 else x.contiguous())
+        rv, wi, wo = dense(router), dense(w_in), dense(w_out)
+        beta = None if ln is None or len(ln) < 2 or ln[1] is None else dense(ln[1]).reshape(-1)
+        out = _hip.moe_rows(xv, rv, wi, wo, dense(b_in), dense(b_out), top_k, dense(residual),
+                            gamma=None if ln is None else dense(ln[0]).reshape(-1), beta=beta, norm=norm, eps=eps,
+                            workspace=workspace)
+        return _wrap(out.reshape(-1), out.shape, x.backend)
+
+    @staticmethod
+    def moe_route(x: Tensor, router: Tensor, top_k: int) -> Tensor:
+        """The constant [rows, E] 0 / 1 mask of the top_k experts router [K, E] picks per row of x
+        [rows, K] (mt_moe_route: the lower index first among equal logits). No history."""
+        xv = _torch_view(x if x._tensor.strides[-1] == 1 else x.contiguous())
+        mask = _hip.moe_route(xv, _torch_view(_dense(router)), top_k, want=("mask",))["mask"]
+        return _wrap(mask.reshape(-1), mask.shape, x.backend)

@@ -17,9 +17,10 @@ import weakref
 
 import numpy as np
 
-from .module import Module
+from .module import Module, Parameter
 from .modules_basic import Dropout, Embedding, FusedLayerNorm, FusedRMSNorm, LayerNorm1d, Linear
 from .nn import GELU, softmax
+from .nn import max as nn_max
 from .rotary import RotaryTable, apply_rope
 from .tensor_functions import tensor, tensor_from_numpy
 
@@ -410,15 +411,102 @@ class FeedForward(Module):
         return h.fused_linear(self.linear_out.weight(), _bias(self.linear_out), residual=flat)
 
 
+class MoEFeedForward(Module):
+    def __init__(self, n_embd: int, middle_dim: int = 256, n_experts: int = 8, top_k: int = 2, p_dropout: float = 0.1,
+                 bias: bool = True, backend=None, fused_step: bool = False):
+        """A mixture-of-experts MLP (Mixtral's rule): router [n_embd, E] gives a logit per expert,
+        the top_k largest are chosen per token (the lower index first among equals), their gates
+        are the softmax over the chosen logits, and the output is the gate-weighted sum of the
+        chosen experts. Expert e is FeedForward(activation="swiglu") on w_in[e] [n_embd, 2
+        middle_dim] (gate columns, then up columns) and w_out[e] [middle_dim, n_embd], with
+        optional biases b_in [E, 2 middle_dim] and b_out [E, n_embd]."""
+        super().__init__()
+        if not 2 <= n_experts <= 64 or not 1 <= top_k <= min(n_experts, 8):
+            raise ValueError(f"MoEFeedForward takes 2 <= n_experts <= 64 and 1 <= top_k <= min(n_experts, 8), got "
+                             f"n_experts = {n_experts}, top_k = {top_k}")
+        self.n_experts, self.top_k, self.middle_dim = int(n_experts), int(top_k), middle_dim
+        self.fused_step = bool(fused_step)
+        param = lambda bound, *shape: Parameter(tensor_from_numpy(  # noqa: E731
+            np.random.uniform(-bound, bound, shape), backend=backend, requires_grad=True))
+        b_in, b_out = (1 / n_embd) ** 0.5, (1 / middle_dim) ** 0.5
+        self.router = param(b_in, n_embd, n_experts)
+        self.w_in = param(b_in, n_experts, n_embd, 2 * middle_dim)
+        self.w_out = param(b_out, n_experts, middle_dim, n_embd)
+        if bias:
+            self.b_in = param(b_in, n_experts, 2 * middle_dim)
+            self.b_out = param(b_out, n_experts, n_embd)
+        self.dropout = Dropout(p_dropout)
+
+    def _mask(self, flat, logits):
+        """The constant [rows, E] 0 / 1 mask of the chosen experts: the routing kernel (mt_moe_route)
+        where the backend has it and the width is one it takes (a multiple of 4, at most 1024);
+        otherwise NumPy with the same tie rule (a stable sort of the negated logits), which reads
+        the logits back to the host. The kernel selects on its own fp32 logits of flat @ router,
+        not on the tensor-op logits the gates are computed from: on a row whose k-th and (k+1)-th
+        logits are within rounding of each other the two may order them differently; the gates
+        are then still the softmax over the set the mask names."""
+        route = getattr(flat.backend, "moe_route", None)
+        if route is not None and flat._tensor.on_device and flat.shape[1] % 4 == 0 and flat.shape[1] <= FUSED_STEP_MAX_WIDTH:
+            return route(flat.detach(), self.router.value.detach(), self.top_k)
+        r = logits.to_numpy()
+        mask = np.zeros(r.shape, dtype=datatype)
+        chosen = np.argsort(-r, axis=1, kind="stable")[:, :self.top_k]
+        np.put_along_axis(mask, chosen, 1.0, axis=1)
+        mask[~np.isfinite(r).all(axis=1)] = 0.0  # a non-finite logit: the row's gates are 0 / 0
+        return tensor_from_numpy(mask, backend=flat.backend)
+
+    def forward(self, x):
+        """The general path (training, the prefill, more than 64 rows, a backend without the
+        kernel), in tensor ops and differentiable: the router logits, the chosen set as a constant
+        0 / 1 mask, the gates exp(r - max) * mask / sum, and EVERY expert computed densely on all
+        rows and weighted by its gate column. That is E / top_k times the arithmetic and weight
+        traffic of the routed computation: the simple correct path, not the fast one (the cached
+        step's is forward_fused)."""
+        batch_size, seq_len, n_embd = x.shape
+        rows, E, F, n_out = batch_size * seq_len, self.n_experts, self.middle_dim, self.w_out.value.shape[2]
+        flat = x.contiguous().view(rows, n_embd)
+        logits = flat @ self.router.value
+        mask = self._mask(flat, logits)
+        top = nn_max(logits.detach(), 1)  # a constant shift: the gates and their gradient do not depend on it
+        ex = (logits - top).exp() * mask
+        gates = ex / ex.sum(1)
+        h = flat.view(1, rows, n_embd) @ self.w_in.value  # [E, rows, 2F]
+        if self.b_in is not None:
+            h = h + self.b_in.value.view(E, 1, 2 * F)
+        h = h.contiguous().view(E * rows, 2 * F).swiglu().view(E, rows, F)
+        y = h @ self.w_out.value  # [E, rows, n_out]
+        if self.b_out is not None:
+            y = y + self.b_out.value.view(E, 1, n_out)
+        out = (y * gates.permute(1, 0).contiguous().view(E, rows, 1)).sum(0)
+        return self.dropout(out.view(rows, n_out)).view(batch_size, seq_len, n_out)
+
+    def forward_fused(self, flat, ln):
+        """forward for a cached step, one call of the mixture-of-experts kernel (Tensor.moe_mlp):
+        flat [rows <= 64, n_embd] is the un-normalised input, ln the block's norm (the prologue);
+        only the chosen experts' weights are read. Returns [rows, n_embd]: moe(ln(flat)) + flat.
+        The kernel's workspace belongs to this module: one buffer, sized for the largest step (64
+        rows), allocated at the first call and kept for the module's life, so a captured decode
+        graph that recorded its address can replay for as long as the model exists."""
+        val = lambda p: None if p is None else p.value  # noqa: E731
+        if self._workspace is None:
+            E, K, F2 = self.w_in.value.shape
+            self._workspace = flat.backend.moe_workspace(flat, FUSED_STEP_MAX_ROWS, K, F2 // 2, self.w_out.value.shape[2],
+                                                         E, self.top_k)
+        return flat.moe_mlp(self.router.value, self.w_in.value, self.w_out.value, val(self.b_in), val(self.b_out),
+                            top_k=self.top_k, residual=flat, workspace=self._workspace, **_norm_kw(ln))
+
+
 class TransformerLayer(Module):
     """Pre-LN transformer block (reference :279-362)."""
 
     def __init__(self, n_embd: int, n_head: int, p_dropout: float = 0.1, ln_eps: float = 1e-8,
                  bias: bool = True, backend=None, use_fused_kernel: bool = False,
                  use_flash_attention: bool = False, causal: bool = True, n_kv_head=None, rope=None,
-                 fused_step: bool = False, norm: str = "layer", mlp: str = "gelu"):
+                 fused_step: bool = False, norm: str = "layer", mlp: str = "gelu", n_experts: int = 8,
+                 moe_top_k: int = 2):
         """norm: "layer" (LayerNorm) or "rms" (FusedRMSNorm with eps = ln_eps); mlp: "gelu" or
-        "swiglu" (FeedForward(activation=...)).
+        "swiglu" (FeedForward(activation=...)), or "moe": MoEFeedForward with n_experts gated
+        experts of which every token takes moe_top_k.
         fused_step (needs use_fused_kernel=True: the layer norms must be FusedLayerNorm): a
         decode or extend step of at most 64 rows on a filled cache runs on the fused skinny linear
         (_forward_fused); the prefill, larger steps, live dropout and a call without a cache take
@@ -434,7 +522,12 @@ class TransformerLayer(Module):
                                             use_fused_kernel=use_fused_kernel,
                                             use_flash_attention=use_flash_attention, n_kv_head=n_kv_head,
                                             rope=rope, fused_step=fused_step)
-        self.ff = FeedForward(n_embd, 256, p_dropout, bias, backend, fused_step=fused_step, activation=mlp)
+        if mlp not in ("gelu", "swiglu", "moe"):
+            raise ValueError(f'mlp must be "gelu", "swiglu" or "moe", got {mlp!r}')
+        if mlp == "moe":
+            self.ff = MoEFeedForward(n_embd, 256, n_experts, moe_top_k, p_dropout, bias, backend, fused_step=fused_step)
+        else:
+            self.ff = FeedForward(n_embd, 256, p_dropout, bias, backend, fused_step=fused_step, activation=mlp)
         self.use_fused_kernel = use_fused_kernel
         self.ln_1 = _make_norm(norm, n_embd, ln_eps, backend, use_fused_kernel)
         self.ln_2 = _make_norm(norm, n_embd, ln_eps, backend, use_fused_kernel)
@@ -473,9 +566,13 @@ class DecoderLM(Module):
                  p_dropout: float = 0.1, ln_eps: float = 1e-5, bias: bool = True, backend=None,
                  use_fused_kernel: bool = False, use_flash_attention: bool = False, n_layer: int = 4,
                  n_kv_head=None, pos_encoding: str = "learned", rope_theta: float = 10000.0,
-                 fused_step: bool = False, norm: str = "layer", mlp: str = "gelu"):
+                 fused_step: bool = False, norm: str = "layer", mlp: str = "gelu", n_experts: int = 8,
+                 moe_top_k: int = 2):
         """norm: "layer", or "rms" for RMSNorm (eps = ln_eps) in every block and before lm_head;
-        mlp: "gelu", or "swiglu" for the gated MLP silu(x W_gate) * (x W_up). With rope and
+        mlp: "gelu", or "swiglu" for the gated MLP silu(x W_gate) * (x W_up), or "moe" for a
+        mixture of n_experts such gated MLPs of which a router gives every token moe_top_k
+        (MoEFeedForward; a fused_step model runs the cached step's on the routed expert kernels,
+        mt_moe_rows, which read the chosen experts' weights only). With rope and
         n_kv_head these make a Llama-shaped model; every path of the model (training, the cache,
         fused_step, graph, speculate) takes them.
         fused_step (needs use_fused_kernel=True; fixed at construction): every decode or extend
@@ -514,7 +611,8 @@ class DecoderLM(Module):
             setattr(self, f"t_layer_{i + 1}", TransformerLayer(
                 n_embd, n_head, p_dropout, ln_eps, bias, backend,
                 use_fused_kernel=use_fused_kernel, use_flash_attention=use_flash_attention,
-                n_kv_head=n_kv_head, rope=self.rope, fused_step=fused_step, norm=norm, mlp=mlp))
+                n_kv_head=n_kv_head, rope=self.rope, fused_step=fused_step, norm=norm, mlp=mlp, n_experts=n_experts,
+                moe_top_k=moe_top_k))
         self.dropout = Dropout(p_dropout)
         self.lm_head = Linear(n_embd, n_vocab, bias, backend)
         self.use_fused_kernel = use_fused_kernel
@@ -526,6 +624,7 @@ class DecoderLM(Module):
         self.graph_captures = 0  # hipGraph captures of the decode step (generate(graph=True))
         self.spec_stats = None   # the last generate(speculate=...) call's counters
         self.quantized = None    # the format quantize_weights stored the linears' weights in
+        self.mlp = mlp
 
     def _linears(self):
         """(name, Linear, gated) of every linear quantize_weights stores: each block's Q / K / V
@@ -563,6 +662,9 @@ class DecoderLM(Module):
         if not self.fused_step:
             raise ValueError("quantize_weights needs a model built with fused_step=True (the cached step runs the "
                              "quantised skinny linear)")
+        if self.mlp == "moe":
+            raise ValueError('quantize_weights: a mixture-of-experts model (mlp="moe") keeps fp32 weights; quantised '
+                             "experts are not supported")
         if self.quantized is not None:
             raise ValueError(f"the weights are already stored as {self.quantized}")
         if fmt not in _hip.WEIGHT_FORMATS:

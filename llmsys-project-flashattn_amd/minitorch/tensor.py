@@ -411,6 +411,22 @@ class Tensor:
         return fn(self, [weight], None if bias is None else [bias], None if residual is None else [residual],
                   ln, gelu, **kw)[0]
 
+    def moe_mlp(self, router, w_in, w_out, b_in=None, b_out=None, top_k=2, residual=None, norm=None, eps=None,
+                ln=None, workspace=None):
+        """Generation: self [M <= 64, K] through the mixture-of-experts MLP kernel (mt_moe_rows):
+        (+ residual) sum_j gate_j expert_j(norm(self)) over the top_k experts that router [K, E]
+        picks per row (softmax over the chosen logits; the lower index first among equals), expert e
+        the gated MLP silu(xh w_in[e][:, :F]) * (xh w_in[e][:, F:]) @ w_out[e] with w_in [E, K, 2F],
+        w_out [E, F, N] and optional biases b_in [E, 2F], b_out [E, N]. ln / norm / eps as
+        fused_linear. workspace: a buffer from backend.moe_workspace that the caller owns (it must
+        outlive every captured graph that recorded this call), or None for one allocated per call.
+        Only the chosen experts' weights are read. Inference only: the result has no
+        history; a backend without the kernel raises."""
+        fn = getattr(self.backend, "moe_mlp", None)
+        if fn is None:
+            raise NotImplementedError("this backend has no mixture-of-experts kernel (HipKernelOps has)")
+        return fn(self, router, w_in, w_out, b_in, b_out, top_k, residual, norm, eps, ln, workspace)
+
     def rope(self, table, pos0=None) -> "Tensor":
         """Rotary position embedding of the head rows of self [B,H,T,d] by a RotaryTable: token t
         of batch row b is rotated to position min(max(pos0[b], 0) + t, n_positions - 1) (pos0: a

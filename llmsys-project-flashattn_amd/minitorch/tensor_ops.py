@@ -151,6 +151,11 @@ class TensorBackend:
         # the fused skinny linear of a cached decode step (optional: DecoderLM(fused_step=True)
         # needs it)
         self.fused_linear = getattr(ops, "fused_linear", None)
+        # the mixture-of-experts MLP of a cached step and its routing stage (optional:
+        # DecoderLM(mlp="moe", fused_step=True) needs them)
+        self.moe_mlp = getattr(ops, "moe_mlp", None)
+        self.moe_route = getattr(ops, "moe_route", None)
+        self.moe_workspace = getattr(ops, "moe_workspace", None)
         # rotary position embedding as one kernel (optional: a backend without it runs the tensor-op form)
         self.rope = getattr(ops, "rope", None)
         # RMSNorm and SwiGLU as one kernel each way (optional: a backend without them runs tensor ops)

@@ -1181,11 +1181,13 @@ def bench_fused_kernel(torch, minitorch, _hip, M, K, N, rounds, warmup, inner=32
     return out
 
 
-def _graph_kernel_nodes(torch, lm):
-    """Kernel nodes of the model's captured decode-step graphs (newest entry): torch's debug dump
-    is not used; the count comes from replaying under the profiler."""
+def _graph_kernel_nodes(torch, lm, slot=None):
+    """Kernel nodes of the model's captured decode-step graphs (newest entry, or the newest of the
+    entry `slot`, e.g. a batch size): torch's debug dump is not used; the count comes from
+    replaying under the profiler."""
     from torch.profiler import ProfilerActivity, profile
-    graphs = [g for e in lm._decode_graphs.values() for g, _ in e["graphs"].values()]
+    entries = lm._decode_graphs.values() if slot is None else [lm._decode_graphs[slot]]
+    graphs = [g for e in entries for g, _ in e["graphs"].values()]
     g = graphs[-1]
     g.replay()
     torch.cuda.synchronize()
@@ -1324,6 +1326,96 @@ def fused_legs(args, torch, minitorch, _hip):
         json.dump(res, f, indent=1)
 
 
+def bench_moe_kernel(torch, minitorch, _hip, M, K, F, E, k, rounds, warmup, inner=32):
+    """mt_moe_rows (RMSNorm + router + top-k + the chosen experts + residual, 4 launches) at width K =
+    N, against the dense gated pair of mt_linear_rows_ex launches (RMSNorm + gated linear_in, then
+    linear_out + residual) at the same F (one expert's size) and at F E (a dense model holding the
+    same parameters), and against a device copy of the bytes the step must read: the weights of the
+    experts its rows chose. bench_llama_kernel's conventions."""
+    hip = minitorch.TensorBackend(minitorch.HipKernelOps)
+    rng = np.random.default_rng(0)
+    t = lambda a: minitorch.tensor_from_numpy(np.ascontiguousarray(a, dtype=np.float32), hip)  # noqa: E731
+    u = lambda n, *s: t(rng.uniform(-n ** -0.5, n ** -0.5, s))  # noqa: E731
+    x, gamma = t(rng.normal(0.5, 1, (M, K))), t(1 + 0.3 * rng.standard_normal(K))
+    router, w_in, w_out = u(K, K, E), u(K, E, K, 2 * F), u(F, E, F, K)
+    dense = {f: (u(K, K, 2 * f), u(f, f, K)) for f in (F, F * E)}
+    ln = dict(ln=(gamma, None), norm="rms", eps=1e-5)
+    from minitorch.hip_kernel_ops import _torch_view
+    idx = torch.empty((M, k), dtype=torch.int32, device="cuda")
+    _hip.moe_rows(_torch_view(x), _torch_view(router), _torch_view(w_in), _torch_view(w_out), top_k=k,
+                  gamma=_torch_view(gamma), norm="rms", eps=1e-5, topk_idx=idx)
+    chosen = int(torch.unique(idx).numel())
+    step_bytes = 4 * (K * E + chosen * (K * 2 * F + F * K))
+    copy_src, copy_dst = torch.empty(step_bytes // 4, device="cuda"), torch.empty(step_bytes // 4, device="cuda")
+    # (linear_out of the F E model has an input width past the skinny kernel's 1024: rocBLAS and an add there)
+    pair = lambda f: lambda i: (x.fused_linear(dense[f][0], glu=True, **ln).fused_linear(dense[f][1], residual=x)  # noqa: E731
+                                if f <= 1024 else x.fused_linear(dense[f][0], glu=True, **ln) @ dense[f][1] + x)
+    legs = {"moe": _graph_of(torch, lambda i: x.moe_mlp(router, w_in, w_out, top_k=k, residual=x, **ln), inner),
+            "dense_pair_F": _graph_of(torch, pair(F), inner),
+            "dense_pair_FE": _graph_of(torch, pair(F * E), inner),
+            "copy_of_step_bytes": _graph_of(torch, lambda i: copy_dst.copy_(copy_src), inner)}
+    out = {"M": M, "K": K, "F": F, "E": E, "k": k, "rounds": rounds, "calls_per_replay": inner, "experts_chosen": chosen,
+           "step_bytes": step_bytes, "all_expert_bytes": 4 * E * (K * 2 * F + F * K),
+           **_alternate(torch, legs, rounds, warmup, inner)}
+    for name in ("dense_pair_F", "dense_pair_FE", "copy_of_step_bytes"):
+        out[f"{name}_over_moe"] = out[f"{name}_s_median"] / out["moe_s_median"]
+    return out
+
+
+def bench_generate_moe(torch, minitorch, n_positions, prompt_len, new_tokens, batch, rounds):
+    """generate(graph=True) tokens/s of the MoE model (8 experts, top 2) against the dense SwiGLU
+    model (one expert's size), both Llama-shaped with fused_step=True; kernels per replayed step."""
+    backend = minitorch.TensorBackend(minitorch.HipKernelOps)
+    rng = np.random.default_rng(0)
+    prompts = [[int(t) for t in rng.integers(0, 10000, prompt_len)] for _ in range(batch)]
+    lms = {}
+    for name, mlp in (("swiglu", dict(mlp="swiglu")), ("moe", dict(mlp="moe", n_experts=8, moe_top_k=2))):
+        np.random.seed(0)
+        lms[name] = minitorch.DecoderLM(n_vocab=10000, n_embd=256, n_head=8, n_positions=n_positions, p_dropout=0.0,
+                                        backend=backend, use_fused_kernel=True, use_flash_attention=True, fused_step=True,
+                                        norm="rms", pos_encoding="rope", n_kv_head=2, **mlp)
+    legs = {}
+    for name, lm in lms.items():
+        legs[f"{name}_one"] = lambda lm=lm: lm.generate(prompts[:1], new_tokens, graph=True)
+        legs[f"{name}_batch"] = lambda lm=lm: lm.generate(prompts, new_tokens, graph=True)
+    for fn in legs.values():  # warm-up: captures the graphs
+        fn()
+    nodes = {}
+    for name, lm in lms.items():
+        try:
+            nodes[name] = _graph_kernel_nodes(torch, lm, slot=batch)  # the same graph of both: the batch's greedy step
+        except Exception as e:  # the profiler is optional: the count is then reported as missing
+            nodes[name] = f"not counted: {type(e).__name__}"
+    rate = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():  # alternated in one process
+            t0 = time.perf_counter()
+            toks = fn()
+            rate[k].append(sum(len(t) for t in toks) / (time.perf_counter() - t0))
+    med = {k: statistics.median(v) for k, v in rate.items()}
+    return {"n_positions": n_positions, "prompt_len": prompt_len, "new_tokens": new_tokens, "batch": batch,
+            "rounds": rounds, "kernels_per_replayed_step_batch": nodes,
+            **{f"{k}_tokens_per_s_median": v for k, v in med.items()},
+            **{f"{k}_tokens_per_s_best": max(v) for k, v in rate.items()},
+            **{f"moe_over_swiglu_{k}": med[f"moe_{k}"] / med[f"swiglu_{k}"] for k in ("one", "batch")}}
+
+
+def moe_legs(args, torch, minitorch, _hip):
+    res = {"device": torch.cuda.get_device_name(0), "kernel": [], "generate": []}
+    for M in (1, 8, 64):
+        r = bench_moe_kernel(torch, minitorch, _hip, M, 256, 256, 8, 2, args.rounds, args.warmup)
+        print(json.dumps(r), flush=True)
+        res["kernel"].append(r)
+    if not args.skip_generate:
+        for npos, plen, new, batch, rounds in ((40, 8, 32, 8, 5), (1024, 768, 128, 8, 3)):
+            r = bench_generate_moe(torch, minitorch, npos, plen, new, batch, rounds)
+            print(json.dumps(r), flush=True)
+            res["generate"].append(r)
+    os.makedirs(os.path.dirname(args.moe_out), exist_ok=True)
+    with open(args.moe_out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 WQ_FORMATS = ("bf16", "fp8", "int4")
 
 
@@ -1442,6 +1534,10 @@ def main():
                     help="the Llama-shaped block: the gated fused linear and RMSNorm against what they replace, and "
                          "generate(graph=True) of DecoderLM(norm=\"rms\", mlp=\"swiglu\") with and without fused_step")
     ap.add_argument("--llama-out", default=os.path.join(ROOT, "profiles", "llama_block_bench.json"))
+    ap.add_argument("--moe-legs", action="store_true",
+                    help="the mixture-of-experts MLP kernel against the dense gated pair and a copy of the step's bytes, "
+                         "and generate(graph=True) of the MoE model against the dense SwiGLU model")
+    ap.add_argument("--moe-out", default=os.path.join(ROOT, "profiles", "moe_bench.json"))
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--skip-generate", action="store_true")
@@ -1455,6 +1551,8 @@ def main():
         _hip.use_library(os.path.abspath(args.lib), allow_missing=True)
     if args.wq_legs:
         return wq_legs(args, torch, minitorch, _hip)
+    if args.moe_legs:
+        return moe_legs(args, torch, minitorch, _hip)
     if args.fused_legs:
         return fused_legs(args, torch, minitorch, _hip)
     if args.llama_legs:
