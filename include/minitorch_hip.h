@@ -646,6 +646,52 @@ int mt_moe_rows(const float* x, int64_t ldx, int64_t M, int64_t K, int norm, con
                 const float* residual, float* out, int32_t* topk_idx, float* topk_gate, void* workspace,
                 int64_t workspace_bytes, void* stream);
 
+/* ---- routed mixture-of-experts for any number of rows: sort, grouped GEMM, combine (fp32) ----
+ * The training and prefill path of the MLP above. The P = M k (row, slot) entries of topk_idx
+ * [M, k] (mt_moe_route's; -1, or any value outside 0..E-1, drops the entry) are sorted by expert
+ * once and every product runs over the sorted segments. Products on v_mfma_f32_32x32x2_f32; no
+ * atomics; nothing is allocated; stream-ordered and capturable; every grid depends on the host
+ * arguments alone and no count is read back. 1 <= M, M k < 2^31, 2 <= E <= 64, 1 <= k <= min(E, 8).
+ * mt_moe_sort: offsets [E + 1], the exclusive scan of the experts' counts; perm [P], sorted
+ *   position -> entry m k + j, ascending inside a segment (a stable sort), -1 from offsets[E] on;
+ *   pos [M, k], the inverse, -1 for a dropped entry. Optional (NULL to skip): row [P] = perm / k,
+ *   the row an entry came from, and, with gates [M, E], gate [P] = gates[row, expert] (the two go
+ *   together). Entries past offsets[E] of row and gate are not written. The workspace of
+ *   mt_moe_sort_workspace_bytes is the caller's. Three launches.
+ * mt_moe_grouped_gemm, for every expert e and sorted position p in [offsets[e], offsets[e + 1]):
+ *   form 0 (NN)  C[p, :] = s[p] (A[src[p], :] @ W[e] + bias[e]),  B = W [E, Kd, N], C [P, N]
+ *   form 1 (NT)  C[p, :] = s[p] (A[src[p], :] @ W[e]^T),          B = W [E, N, Kd], C [P, N]
+ *   form 2 (TN)  C[e] = sum_p A[src[p], :]^T (s[p] B[srcb[p], :]), C [E, Kd, N] (Kd: the width of A),
+ *                db[e] = sum_p s[p] B[srcb[p], :], db [E, N] or NULL; an empty expert gets zeros.
+ *   A [a_rows, Kd] and (TN) B [b_rows, N] dense; src, srcb [P] int32 or NULL (the position itself;
+ *   an index is held inside the matrix); s [P] or NULL; bias [E, N] or NULL, NN only. Kd and N are
+ *   multiples of 4 in 4..2^20; A, B, C, bias and db are 16-byte aligned. Rows of C past offsets[E]
+ *   are not written. Tiles of MT_MOE_GROUPED_TM rows; NN / NT launch floor(P / TM) + E row tiles,
+ *   and a surplus workgroup or an empty expert touches no weight. Every output element is one
+ *   accumulation chain in ascending reduction index (TN: ascending p; db in four interleaved parts
+ *   combined in a fixed order), then the bias, then the scale: the bits of an NN / NT row depend
+ *   on its A row, W[e], the bias and the sizes, not on M, the tile or the rows beside it.
+ * mt_moe_combine: out[m] = residual[m] + (((g0 y[pos(m,0)]) + g1 y[pos(m,1)]) + ...), g(m,j) =
+ *   gates[m, topk_idx[m,j]] from the dense gates [M, E]; gates and topk_idx NULL: a plain sum.
+ *   y [P, N], residual [M, N] or NULL, out [M, N]. A row with a dropped entry is NaN.
+ * mt_moe_gate_grad: dgate [M, E] = <dout[m], y[pos(m,j)]> at column topk_idx[m,j], 0 elsewhere;
+ *   one wave per (row, slot), a fixed shuffle tree. N a multiple of 4 in 4..2^20 for both.
+ * Refused before any device call: a size out of range, k > E, an unknown form, a NULL or misaligned
+ * pointer, a bias / srcb / db given to a form that has none, a workspace that is too small. */
+#define MT_MOE_GROUPED_TM 64
+int mt_moe_sort_workspace_bytes(int64_t M, int64_t E, int64_t k, int64_t* bytes);
+int mt_moe_sort(const int32_t* topk_idx, const float* gates, int64_t M, int64_t E, int64_t k, int32_t* offsets,
+                int32_t* perm, int32_t* pos, int32_t* row, float* gate, void* workspace, int64_t workspace_bytes,
+                void* stream);
+int mt_moe_grouped_gemm(int form, const float* A, int64_t a_rows, const int32_t* src, const float* s,
+                        const float* B, int64_t b_rows, const int32_t* srcb, const float* bias,
+                        const int32_t* offsets, int64_t P, int64_t E, int64_t Kd, int64_t N, float* C, float* db,
+                        void* stream);
+int mt_moe_combine(const float* y, const int32_t* pos, const float* gates, const int32_t* topk_idx,
+                   const float* residual, float* out, int64_t M, int64_t N, int64_t E, int64_t k, void* stream);
+int mt_moe_gate_grad(const float* dout, const float* y, const int32_t* pos, const int32_t* topk_idx, float* dgate,
+                     int64_t M, int64_t N, int64_t E, int64_t k, void* stream);
+
 /* ---- RMSNorm and SwiGLU (a Llama-shaped block's training path), device pointers (fp32) ----
  * RMSNorm over the last dim of [rows, hidden]: rstd[r] = 1 / sqrt(mean_j x[r,j]^2 + eps),
  * out = gamma (x rstd). Backward, with g = gamma dy: dx = rstd g - x rstd^3 (sum_j g_j x_j) / hidden,

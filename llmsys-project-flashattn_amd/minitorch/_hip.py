@@ -122,6 +122,12 @@ _PROTOS = {
                             _vp]),
     "mt_moe_rows": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _vp, ctypes.c_float, _vp, _i64, _i64, _vp, _vp, _i64,
                            _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mt_moe_sort_workspace_bytes": (_int, [_i64, _i64, _i64, _i64p]),
+    "mt_moe_sort": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mt_moe_grouped_gemm": (_int, [_int, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp,
+                                   _vp, _vp]),
+    "mt_moe_combine": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
+    "mt_moe_gate_grad": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "mt_rmsnorm_fw": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_float, _vp]),
     "mt_rmsnorm_bw_workspace_bytes": (_i64, [_i64, _i64]),
     "mt_rmsnorm_bw": (_int, [_vp] * 6 + [_i64, _i64, _vp, _vp]),
@@ -1367,6 +1373,162 @@ def moe_rows(x, router, w_in, w_out, b_in=None, b_out=None, top_k=2, residual=No
                             workspace.numel(), st), "mt_moe_rows")
     moe_rows_calls += 1
     return out
+
+
+moe_grouped_calls = 0  # routed forwards through moe_routed_fw (tests tell the path by it)
+MOE_GROUPED_TM = 64    # the grouped GEMM's row tile (MT_MOE_GROUPED_TM)
+MOE_FORMS = {"nn": 0, "nt": 1, "tn": 2}
+
+
+def _moe_t(fn, name, t, shape, dtype=None):
+    """Pointer of a dense device tensor of this shape (None stays None)."""
+    torch = _torch()
+    dtype = dtype or torch.float32
+    if t is None:
+        return None
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or not t.is_cuda:
+        raise ValueError(f"{fn}: {name} must be a dense device {dtype} {list(shape)} tensor")
+    return t.data_ptr()
+
+
+def moe_sort(topk_idx, E: int, gates=None, stream: Optional[int] = None):
+    """The (row, slot) entries of topk_idx [M, k] int32 sorted by expert (mt_moe_sort): a dict of
+    offsets [E + 1], perm [M k] (sorted position -> entry, stable, -1 past offsets[E]), pos [M, k]
+    (the inverse, -1 for a dropped entry), row [M k] = perm // k and, with gates [M, E], gate [M k]
+    = gates[row, expert]; row and gate are written up to offsets[E] only. No host read-back."""
+    torch = _torch()
+    fn = "moe_sort"
+    if topk_idx.dim() != 2:
+        raise ValueError(f"{fn}: topk_idx must be [M, k], got {tuple(topk_idx.shape)}")
+    M, k = topk_idx.shape
+    _moe_t(fn, "topk_idx", topk_idx, (M, k), torch.int32)
+    gp = _moe_t(fn, "gates", gates, (M, E))
+    need = ctypes.c_int64(0)
+    check(lib().mt_moe_sort_workspace_bytes(M, E, k, ctypes.byref(need)), "mt_moe_sort_workspace_bytes")
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=topk_idx.device)  # noqa: E731
+    out = dict(offsets=i32(E + 1), perm=i32(M * k), pos=i32(M, k), row=i32(M * k))
+    if gates is not None:
+        out["gate"] = torch.empty(M * k, dtype=torch.float32, device=topk_idx.device)
+    ws = i32(max(1, need.value // 4))
+    st = stream_ptr(topk_idx.device) if stream is None else stream
+    check(lib().mt_moe_sort(topk_idx.data_ptr(), gp, M, E, k, out["offsets"].data_ptr(), out["perm"].data_ptr(),
+                            out["pos"].data_ptr(), out["row"].data_ptr(),
+                            out["gate"].data_ptr() if gates is not None else None, ws.data_ptr(), ws.numel() * 4, st),
+          "mt_moe_sort")
+    return out
+
+
+def moe_grouped_gemm(form: str, A, B, offsets, src=None, s=None, bias=None, srcb=None, want_db=False,
+                     stream: Optional[int] = None):
+    """The grouped GEMM over the sorted segments (mt_moe_grouped_gemm; fp32), P = len(src) or
+    A's rows: "nn" C[p] = s[p] (A[src[p]] @ B[e] + bias[e]) with B [E, Kd, N]; "nt" C[p] = s[p]
+    (A[src[p]] @ B[e]^T) with B [E, N, Kd]; both return C [P, N] (rows past offsets[E] are not
+    written). "tn" returns (dW [E, Ka, N], db [E, N] or None) = (sum_p A[src[p]]^T (s[p] B[srcb[p]]),
+    sum_p s[p] B[srcb[p]]) over each expert's segment, A [*, Ka], B [*, N]."""
+    torch = _torch()
+    fn = "moe_grouped_gemm"
+    if form not in MOE_FORMS:
+        raise ValueError(f'{fn}: form must be "nn", "nt" or "tn", got {form!r}')
+    _check_dev(A, B, offsets)
+    E = offsets.numel() - 1
+    if A.dim() != 2:
+        raise ValueError(f"{fn}: A must be 2-D, got {tuple(A.shape)}")
+    P = next((t.numel() for t in (src, srcb, s) if t is not None), A.shape[0])
+    Kd = A.shape[1]
+    if form == "tn":
+        if B.dim() != 2:
+            raise ValueError(f"{fn}: the tn form takes B [rows, N], got {tuple(B.shape)}")
+        N, bshape, cshape = B.shape[1], tuple(B.shape), (E, Kd, B.shape[1])
+    else:
+        if B.dim() != 3:
+            raise ValueError(f"{fn}: the {form} form takes stacked weights B [E, ., .], got {tuple(B.shape)}")
+        N = B.shape[2] if form == "nn" else B.shape[1]
+        bshape, cshape = (E, Kd, N) if form == "nn" else (E, N, Kd), (P, N)
+    ptrs = [_moe_t(fn, "A", A, A.shape), _moe_t(fn, "src", src, (P,), torch.int32), _moe_t(fn, "s", s, (P,)),
+            _moe_t(fn, "B", B, bshape), _moe_t(fn, "srcb", srcb, (P,), torch.int32), _moe_t(fn, "bias", bias, (E, N)),
+            _moe_t(fn, "offsets", offsets, (E + 1,), torch.int32)]
+    C = torch.empty(cshape, dtype=torch.float32, device=A.device)
+    db = torch.empty((E, N), dtype=torch.float32, device=A.device) if want_db else None
+    st = stream_ptr(A.device) if stream is None else stream
+    check(lib().mt_moe_grouped_gemm(MOE_FORMS[form], ptrs[0], A.shape[0], ptrs[1], ptrs[2], ptrs[3],
+                                    B.shape[0] if form == "tn" else 0, ptrs[4], ptrs[5], ptrs[6], P, E, Kd, N,
+                                    C.data_ptr(), None if db is None else db.data_ptr(), st), "mt_moe_grouped_gemm")
+    return (C, db) if form == "tn" else C
+
+
+def moe_combine(y, pos, gates=None, topk_idx=None, residual=None, E: Optional[int] = None,
+                stream: Optional[int] = None):
+    """out [M, N] = residual + sum_j gates[m, topk_idx[m, j]] y[pos[m, j]] in ascending slot order
+    (mt_moe_combine); without gates a plain sum. A row with pos -1 is NaN."""
+    torch = _torch()
+    fn = "moe_combine"
+    M, k = pos.shape
+    N = y.shape[1]
+    E = gates.shape[1] if gates is not None else (E or max(2, k))
+    args = [_moe_t(fn, "y", y, (M * k, N)), _moe_t(fn, "pos", pos, (M, k), torch.int32), _moe_t(fn, "gates", gates, (M, E)),
+            _moe_t(fn, "topk_idx", topk_idx, (M, k), torch.int32), _moe_t(fn, "residual", residual, (M, N))]
+    out = torch.empty((M, N), dtype=torch.float32, device=y.device)
+    st = stream_ptr(y.device) if stream is None else stream
+    check(lib().mt_moe_combine(*args, out.data_ptr(), M, N, E, k, st), "mt_moe_combine")
+    return out
+
+
+def moe_gate_grad(dout, y, pos, topk_idx, E: int, stream: Optional[int] = None):
+    """dgate [M, E]: <dout[m], y[pos[m, j]]> at column topk_idx[m, j], zero elsewhere (mt_moe_gate_grad)."""
+    torch = _torch()
+    fn = "moe_gate_grad"
+    M, k = pos.shape
+    N = y.shape[1]
+    args = [_moe_t(fn, "dout", dout, (M, N)), _moe_t(fn, "y", y, (M * k, N)), _moe_t(fn, "pos", pos, (M, k), torch.int32),
+            _moe_t(fn, "topk_idx", topk_idx, (M, k), torch.int32)]
+    dgate = torch.empty((M, E), dtype=torch.float32, device=y.device)
+    st = stream_ptr(y.device) if stream is None else stream
+    check(lib().mt_moe_gate_grad(*args, dgate.data_ptr(), M, N, E, k, st), "mt_moe_gate_grad")
+    return dgate
+
+
+def _swiglu(fn, out, *ins, rows, F):
+    check(getattr(lib(), fn)(out.data_ptr(), *[t.data_ptr() for t in ins], rows, F, stream_ptr(out.device)), fn)
+    return out
+
+
+def moe_routed_fw(flat, gates, topk_idx, w_in, w_out, b_in=None, b_out=None):
+    """The routed mixture-of-experts MLP for any number of rows: out [M, N] = sum_j gates[m, e_j]
+    expert_{e_j}(flat[m]) over topk_idx [M, k] (mt_moe_route's), gates the dense [M, E] gate
+    tensor. sort -> NN -> swiglu -> NN -> combine; only the rows routed to an expert meet its
+    weights. Returns (out, saved) with saved what moe_routed_bw needs: gu [M k, 2F] and y [M k, N]
+    at the sorted positions and the sort's outputs."""
+    global moe_grouped_calls
+    torch = _torch()
+    E, F = w_in.shape[0], w_in.shape[2] // 2
+    srt = moe_sort(topk_idx, E, gates)
+    gu = moe_grouped_gemm("nn", flat, w_in, srt["offsets"], src=srt["row"], bias=b_in)
+    h = _swiglu("mt_swiglu_fw", torch.empty((gu.shape[0], F), dtype=torch.float32, device=gu.device), gu,
+                rows=gu.shape[0], F=F)
+    y = moe_grouped_gemm("nn", h, w_out, srt["offsets"], bias=b_out)
+    out = moe_combine(y, srt["pos"], gates, topk_idx)
+    moe_grouped_calls += 1
+    return out, dict(srt, gu=gu, y=y)
+
+
+def moe_routed_bw(dout, saved, flat, topk_idx, w_in, w_out, bias: bool):
+    """(d_flat, d_gates, dW_in, db_in, dW_out, db_out) of moe_routed_fw (the biases' None without
+    bias): the gate gradient from y, dh = (g dout) W_out^T (NT), dW_out / db_out (TN, the rows of
+    dout gathered and scaled by the gate as they are loaded), swiglu's backward on the sorted gu,
+    dW_in / db_in (TN), dxh = dgu W_in^T (NT) and the sum of a row's k slots."""
+    torch = _torch()
+    E, F = w_in.shape[0], w_in.shape[2] // 2
+    off, row, gate, gu = saved["offsets"], saved["row"], saved["gate"], saved["gu"]
+    d_gates = moe_gate_grad(dout, saved["y"], saved["pos"], topk_idx, E)
+    h = _swiglu("mt_swiglu_fw", torch.empty((gu.shape[0], F), dtype=torch.float32, device=gu.device), gu,
+                rows=gu.shape[0], F=F)
+    dw_out, db_out = moe_grouped_gemm("tn", h, dout, off, s=gate, srcb=row, want_db=bias)
+    dh = moe_grouped_gemm("nt", dout, w_out, off, src=row, s=gate)
+    dgu = _swiglu("mt_swiglu_bw", torch.empty_like(gu), dh, gu, rows=gu.shape[0], F=F)
+    dw_in, db_in = moe_grouped_gemm("tn", flat, dgu, off, src=row, want_db=bias)
+    dxh = moe_grouped_gemm("nt", dgu, w_in, off)
+    d_flat = moe_combine(dxh, saved["pos"], E=E)
+    return d_flat, d_gates, dw_in, db_in, dw_out, db_out
 
 
 def scratch_bytes() -> int:

@@ -791,9 +791,36 @@ class HipKernelOps(TensorOps):
         return _wrap(out.reshape(-1), out.shape, x.backend)
 
     @staticmethod
-    def moe_route(x: Tensor, router: Tensor, top_k: int) -> Tensor:
+    def moe_route(x: Tensor, router: Tensor, top_k: int, with_idx: bool = False):
         """The constant [rows, E] 0 / 1 mask of the top_k experts router [K, E] picks per row of x
-        [rows, K] (mt_moe_route: the lower index first among equal logits). No history."""
+        [rows, K] (mt_moe_route: the lower index first among equal logits). No history.
+        with_idx: (mask, topk_idx) instead, topk_idx [rows, top_k] the kernel's int32 indices held
+        bit for bit in a tensor's fp32 storage (a constant for moe_routed_fw / bw, not a number)."""
+        import torch
         xv = _torch_view(x if x._tensor.strides[-1] == 1 else x.contiguous())
-        mask = _hip.moe_route(xv, _torch_view(_dense(router)), top_k, want=("mask",))["mask"]
-        return _wrap(mask.reshape(-1), mask.shape, x.backend)
+        out = _hip.moe_route(xv, _torch_view(_dense(router)), top_k, want=("idx", "mask") if with_idx else ("mask",))
+        mask = _wrap(out["mask"].reshape(-1), out["mask"].shape, x.backend)
+        if not with_idx:
+            return mask
+        return mask, _wrap(out["idx"].view(torch.float32).reshape(-1), out["idx"].shape, x.backend)
+
+    @staticmethod
+    def moe_routed_fw(flat: Tensor, gates: Tensor, topk_idx: Tensor, w_in: Tensor, w_out: Tensor, b_in=None, b_out=None):
+        """The routed mixture-of-experts MLP for any number of rows (mt_moe_sort, mt_moe_grouped_gemm,
+        mt_swiglu_fw, mt_moe_combine): (out [rows, N], what moe_routed_bw needs). topk_idx:
+        moe_route(with_idx=True)'s."""
+        import torch
+        dense = lambda t: None if t is None else _torch_view(_dense(t))  # noqa: E731
+        out, saved = _hip.moe_routed_fw(dense(flat), dense(gates), dense(topk_idx).view(torch.int32), dense(w_in),
+                                        dense(w_out), dense(b_in), dense(b_out))
+        return _wrap(out.reshape(-1), out.shape, flat.backend), saved
+
+    @staticmethod
+    def moe_routed_bw(out_grad: Tensor, saved, flat: Tensor, topk_idx: Tensor, w_in: Tensor, w_out: Tensor, bias: bool):
+        """(d_flat, d_gates, dW_in, db_in, dW_out, db_out) of moe_routed_fw; the biases' are None
+        without bias."""
+        import torch
+        dense = lambda t: _torch_view(_dense(t))  # noqa: E731
+        grads = _hip.moe_routed_bw(dense(out_grad), saved, dense(flat), dense(topk_idx).view(torch.int32), dense(w_in),
+                                   dense(w_out), bias)
+        return tuple(None if g is None else _wrap(g.reshape(-1), g.shape, flat.backend) for g in grads)

@@ -22,7 +22,7 @@ from .modules_basic import Dropout, Embedding, FusedLayerNorm, FusedRMSNorm, Lay
 from .nn import GELU, softmax
 from .nn import max as nn_max
 from .rotary import RotaryTable, apply_rope
-from .tensor_functions import tensor, tensor_from_numpy
+from .tensor_functions import MoERouted, tensor, tensor_from_numpy
 
 # Small host-built index tensors the model makes on every forward (the [B] key-padding lengths
 # of the flash path, the [1, T] position ids): cached by value, so a training loop that feeds
@@ -413,19 +413,25 @@ class FeedForward(Module):
 
 class MoEFeedForward(Module):
     def __init__(self, n_embd: int, middle_dim: int = 256, n_experts: int = 8, top_k: int = 2, p_dropout: float = 0.1,
-                 bias: bool = True, backend=None, fused_step: bool = False):
+                 bias: bool = True, backend=None, fused_step: bool = False, routed: bool = False):
         """A mixture-of-experts MLP (Mixtral's rule): router [n_embd, E] gives a logit per expert,
         the top_k largest are chosen per token (the lower index first among equals), their gates
         are the softmax over the chosen logits, and the output is the gate-weighted sum of the
         chosen experts. Expert e is FeedForward(activation="swiglu") on w_in[e] [n_embd, 2
         middle_dim] (gate columns, then up columns) and w_out[e] [middle_dim, n_embd], with
-        optional biases b_in [E, 2 middle_dim] and b_out [E, n_embd]."""
+        optional biases b_in [E, 2 middle_dim] and b_out [E, n_embd].
+        routed: forward runs every expert on the rows routed to it alone (the MoERouted Function:
+        a sort by expert and grouped GEMMs, forward and backward) where the backend has the
+        kernels, the tensor is on the device and n_embd, middle_dim and the output width are
+        multiples of 4 with n_embd <= 1024; anywhere else it takes the dense path below. Unset,
+        nothing changes."""
         super().__init__()
         if not 2 <= n_experts <= 64 or not 1 <= top_k <= min(n_experts, 8):
             raise ValueError(f"MoEFeedForward takes 2 <= n_experts <= 64 and 1 <= top_k <= min(n_experts, 8), got "
                              f"n_experts = {n_experts}, top_k = {top_k}")
         self.n_experts, self.top_k, self.middle_dim = int(n_experts), int(top_k), middle_dim
         self.fused_step = bool(fused_step)
+        self.routed = bool(routed)
         param = lambda bound, *shape: Parameter(tensor_from_numpy(  # noqa: E731
             np.random.uniform(-bound, bound, shape), backend=backend, requires_grad=True))
         b_in, b_out = (1 / n_embd) ** 0.5, (1 / middle_dim) ** 0.5
@@ -455,21 +461,36 @@ class MoEFeedForward(Module):
         mask[~np.isfinite(r).all(axis=1)] = 0.0  # a non-finite logit: the row's gates are 0 / 0
         return tensor_from_numpy(mask, backend=flat.backend)
 
+    def _takes_routed(self, flat):
+        widths = (flat.shape[1], self.middle_dim, self.w_out.value.shape[2])
+        return (self.routed and getattr(flat.backend, "moe_routed_fw", None) is not None
+                and getattr(flat.backend, "moe_route", None) is not None and flat._tensor.on_device
+                and all(w % 4 == 0 for w in widths) and flat.shape[1] <= FUSED_STEP_MAX_WIDTH)
+
     def forward(self, x):
         """The general path (training, the prefill, more than 64 rows, a backend without the
         kernel), in tensor ops and differentiable: the router logits, the chosen set as a constant
         0 / 1 mask, the gates exp(r - max) * mask / sum, and EVERY expert computed densely on all
         rows and weighted by its gate column. That is E / top_k times the arithmetic and weight
         traffic of the routed computation: the simple correct path, not the fast one (the cached
-        step's is forward_fused)."""
+        step's is forward_fused). With routed=True (and _takes_routed) the experts run on the
+        MoERouted Function instead: the same gates, every expert on its own rows only."""
         batch_size, seq_len, n_embd = x.shape
         rows, E, F, n_out = batch_size * seq_len, self.n_experts, self.middle_dim, self.w_out.value.shape[2]
         flat = x.contiguous().view(rows, n_embd)
         logits = flat @ self.router.value
-        mask = self._mask(flat, logits)
+        routed = self._takes_routed(flat)
+        if routed:
+            mask, topk_idx = flat.backend.moe_route(flat.detach(), self.router.value.detach(), self.top_k, with_idx=True)
+        else:
+            mask = self._mask(flat, logits)
         top = nn_max(logits.detach(), 1)  # a constant shift: the gates and their gradient do not depend on it
         ex = (logits - top).exp() * mask
         gates = ex / ex.sum(1)
+        if routed:
+            biases = () if self.b_in is None else (self.b_in.value, self.b_out.value)
+            out = MoERouted.apply(flat, gates, topk_idx, self.w_in.value, self.w_out.value, *biases)
+            return self.dropout(out).view(batch_size, seq_len, n_out)
         h = flat.view(1, rows, n_embd) @ self.w_in.value  # [E, rows, 2F]
         if self.b_in is not None:
             h = h + self.b_in.value.view(E, 1, 2 * F)
@@ -503,10 +524,10 @@ class TransformerLayer(Module):
                  bias: bool = True, backend=None, use_fused_kernel: bool = False,
                  use_flash_attention: bool = False, causal: bool = True, n_kv_head=None, rope=None,
                  fused_step: bool = False, norm: str = "layer", mlp: str = "gelu", n_experts: int = 8,
-                 moe_top_k: int = 2):
+                 moe_top_k: int = 2, moe_routed: bool = False):
         """norm: "layer" (LayerNorm) or "rms" (FusedRMSNorm with eps = ln_eps); mlp: "gelu" or
         "swiglu" (FeedForward(activation=...)), or "moe": MoEFeedForward with n_experts gated
-        experts of which every token takes moe_top_k.
+        experts of which every token takes moe_top_k (moe_routed: MoEFeedForward(routed=...)).
         fused_step (needs use_fused_kernel=True: the layer norms must be FusedLayerNorm): a
         decode or extend step of at most 64 rows on a filled cache runs on the fused skinny linear
         (_forward_fused); the prefill, larger steps, live dropout and a call without a cache take
@@ -525,7 +546,8 @@ class TransformerLayer(Module):
         if mlp not in ("gelu", "swiglu", "moe"):
             raise ValueError(f'mlp must be "gelu", "swiglu" or "moe", got {mlp!r}')
         if mlp == "moe":
-            self.ff = MoEFeedForward(n_embd, 256, n_experts, moe_top_k, p_dropout, bias, backend, fused_step=fused_step)
+            self.ff = MoEFeedForward(n_embd, 256, n_experts, moe_top_k, p_dropout, bias, backend, fused_step=fused_step,
+                                     routed=moe_routed)
         else:
             self.ff = FeedForward(n_embd, 256, p_dropout, bias, backend, fused_step=fused_step, activation=mlp)
         self.use_fused_kernel = use_fused_kernel
@@ -567,12 +589,15 @@ class DecoderLM(Module):
                  use_fused_kernel: bool = False, use_flash_attention: bool = False, n_layer: int = 4,
                  n_kv_head=None, pos_encoding: str = "learned", rope_theta: float = 10000.0,
                  fused_step: bool = False, norm: str = "layer", mlp: str = "gelu", n_experts: int = 8,
-                 moe_top_k: int = 2):
+                 moe_top_k: int = 2, moe_routed: bool = False):
         """norm: "layer", or "rms" for RMSNorm (eps = ln_eps) in every block and before lm_head;
         mlp: "gelu", or "swiglu" for the gated MLP silu(x W_gate) * (x W_up), or "moe" for a
         mixture of n_experts such gated MLPs of which a router gives every token moe_top_k
         (MoEFeedForward; a fused_step model runs the cached step's on the routed expert kernels,
-        mt_moe_rows, which read the chosen experts' weights only). With rope and
+        mt_moe_rows, which read the chosen experts' weights only; moe_routed=True runs training, the
+        prefill and every other step on routed kernels too: a sort by expert and grouped GEMMs over
+        each expert's own rows, forward and backward, instead of every expert on every row. Unset,
+        nothing changes). With rope and
         n_kv_head these make a Llama-shaped model; every path of the model (training, the cache,
         fused_step, graph, speculate) takes them.
         fused_step (needs use_fused_kernel=True; fixed at construction): every decode or extend
@@ -612,7 +637,7 @@ class DecoderLM(Module):
                 n_embd, n_head, p_dropout, ln_eps, bias, backend,
                 use_fused_kernel=use_fused_kernel, use_flash_attention=use_flash_attention,
                 n_kv_head=n_kv_head, rope=self.rope, fused_step=fused_step, norm=norm, mlp=mlp, n_experts=n_experts,
-                moe_top_k=moe_top_k))
+                moe_top_k=moe_top_k, moe_routed=moe_routed))
         self.dropout = Dropout(p_dropout)
         self.lm_head = Linear(n_embd, n_vocab, bias, backend)
         self.use_fused_kernel = use_fused_kernel

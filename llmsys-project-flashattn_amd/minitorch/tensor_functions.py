@@ -451,6 +451,27 @@ class SwiGLU(Function):
         return out_grad.f.swiglu_bw(out_grad, gu)
 
 
+class MoERouted(Function):
+    """The routed mixture-of-experts MLP over flat [rows, K] as backend kernels each way
+    (moe_routed_fw / moe_routed_bw): out = sum_j gates[m, e_j] expert_{e_j}(flat[m]). gates [rows, E]
+    is the differentiable dense gate tensor (the router's gradient flows on through it), topk_idx
+    the constant [rows, k] indices of backend.moe_route(with_idx=True); b_in and b_out come
+    together or not at all."""
+
+    @staticmethod
+    def forward(ctx, flat, gates, topk_idx, w_in, w_out, b_in=None, b_out=None):
+        out, saved = flat.f.moe_routed_fw(flat, gates, topk_idx, w_in, w_out, b_in, b_out)
+        ctx.save_for_backward(saved, flat, topk_idx, w_in, w_out, b_in is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, out_grad):
+        saved, flat, topk_idx, w_in, w_out, bias = ctx.saved_values
+        d_flat, d_gates, dw_in, db_in, dw_out, db_out = out_grad.f.moe_routed_bw(out_grad, saved, flat, topk_idx, w_in,
+                                                                                 w_out, bias)
+        return (d_flat, d_gates, 0.0, dw_in, dw_out) + ((db_in, db_out) if bias else ())
+
+
 def _kv_kw(kv):
     """The optional key-padding lengths (a [B] constant tensor) as the ops' keyword."""
     return {} if kv is None else {"kv_len": kv}

@@ -156,6 +156,10 @@ class TensorBackend:
         self.moe_mlp = getattr(ops, "moe_mlp", None)
         self.moe_route = getattr(ops, "moe_route", None)
         self.moe_workspace = getattr(ops, "moe_workspace", None)
+        # the routed mixture-of-experts MLP for any number of rows, with its backward (optional:
+        # MoEFeedForward(routed=True) takes the dense path without them)
+        self.moe_routed_fw = getattr(ops, "moe_routed_fw", None)
+        self.moe_routed_bw = getattr(ops, "moe_routed_bw", None)
         # rotary position embedding as one kernel (optional: a backend without it runs the tensor-op form)
         self.rope = getattr(ops, "rope", None)
         # RMSNorm and SwiGLU as one kernel each way (optional: a backend without them runs tensor ops)

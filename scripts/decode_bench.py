@@ -121,6 +121,11 @@ PagedKVCaches holding a ragged batch of one row of 4096 tokens and seven of 64.
   generate     generate(graph=True) tokens/s of the quantize_weights model per format against the fp32
                 fused_step model, batch 1 and 8
 
+--moe-grouped-legs instead writes profiles/moe_grouped_bench.json (routed mixture-of-experts for training
+and prefill): MoEFeedForward(256, 256, E = 8, top_k = 2) at 256, 2048 and 16384 rows, routed=True (sort,
+grouped GEMMs, swiglu, combine) against routed=False (the dense tensor-op path of the same module and
+parameters), forward alone and forward + backward, alternated in one process and swapping places each round.
+
 No gate: what is measured is recorded.
 """
 import argparse
@@ -1493,8 +1498,67 @@ def wq_legs(args, torch, minitorch, _hip):
         json.dump(res, f, indent=1)
 
 
+def bench_moe_grouped(torch, minitorch, rows, rounds, warmup, K=256, F=256, E=8, k=2):
+    backend = minitorch.TensorBackend(minitorch.HipKernelOps)
+    ffs = {}
+    for name in ("routed", "dense"):
+        np.random.seed(0)  # the same parameters
+        ffs[name] = minitorch.MoEFeedForward(K, F, E, k, p_dropout=0.0, backend=backend, routed=name == "routed")
+    x = minitorch.tensor_from_numpy(np.random.default_rng(1).standard_normal((1, rows, K)).astype(np.float32), backend,
+                                    requires_grad=True)
+
+    def fw(ff):
+        return lambda i: ff(x)
+
+    def fwbw(ff):
+        def run(i):
+            for p in ff.parameters():
+                p.value.zero_grad_()
+            x.zero_grad_()
+            ff(x).sum().backward()
+        return run
+    legs = {f"{name}_{kind}": make(ff) for kind, make in (("fw", fw), ("fwbw", fwbw)) for name, ff in ffs.items()}
+    inner = max(16, min(128, (1 << 20) // rows))  # windows of tens of milliseconds at every size
+    for fn in legs.values():
+        for i in range(warmup):
+            fn(i)
+    torch.cuda.synchronize()
+    out_r, out_d = ffs["routed"](x).to_numpy(), ffs["dense"](x).to_numpy()
+    names, times = list(legs), {n: [] for n in legs}
+    for r in range(rounds):  # the legs alternate inside every round and swap places between rounds
+        for n in (names if r % 2 == 0 else names[::-1]):
+            times[n].append(_timed(torch, legs[n], inner))
+    med = {n: statistics.median(t) for n, t in times.items()}
+    # the routed path's products: rows k entries through [K, 2F] and [F, K], once forward and twice more backward
+    flops_fw = 2.0 * rows * k * (K * 2 * F + F * K)
+    return {"rows": rows, "K": K, "F": F, "E": E, "top_k": k, "rounds": rounds, "launches_per_timing": inner,
+            **{f"{n}_s_median": med[n] for n in names}, **{f"{n}_s_min": min(times[n]) for n in names},
+            **{f"{n}_s_max": max(times[n]) for n in names},
+            "fw_routed_over_dense": med["routed_fw"] / med["dense_fw"],
+            "fwbw_routed_over_dense": med["routed_fwbw"] / med["dense_fwbw"],
+            "routed_fw_tflops_whole_path": flops_fw / med["routed_fw"] * 1e-12,
+            "routed_fwbw_tflops_whole_path": 3 * flops_fw / med["routed_fwbw"] * 1e-12,
+            "max_abs_routed_minus_dense": float(np.abs(out_r - out_d).max()), "max_abs_out": float(np.abs(out_d).max())}
+
+
+def moe_grouped_legs(args, torch, minitorch, _hip):
+    res = {"device": torch.cuda.get_device_name(0), "rows": []}
+    for rows in (256, 2048, 16384):
+        r = bench_moe_grouped(torch, minitorch, rows, args.rounds, args.warmup)
+        print(json.dumps(r), flush=True)
+        res["rows"].append(r)
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(args.moe_grouped_out), exist_ok=True)
+    with open(args.moe_grouped_out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--moe-grouped-legs", action="store_true",
+                    help="MoEFeedForward routed=True (grouped expert GEMM) against the dense tensor-op path, forward and "
+                         "forward + backward, into --moe-grouped-out")
+    ap.add_argument("--moe-grouped-out", default=os.path.join(ROOT, "profiles", "moe_grouped_bench.json"))
     ap.add_argument("--wq-legs", action="store_true",
                     help="the weight-only quantised skinny linear per format against the fp32 kernel on the same "
                          "values, and generate(graph=True) of a quantize_weights model against the fp32 model")
@@ -1549,6 +1613,8 @@ def main():
     from minitorch import _hip
     if args.lib:
         _hip.use_library(os.path.abspath(args.lib), allow_missing=True)
+    if args.moe_grouped_legs:
+        return moe_grouped_legs(args, torch, minitorch, _hip)
     if args.wq_legs:
         return wq_legs(args, torch, minitorch, _hip)
     if args.moe_legs:
