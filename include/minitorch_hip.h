@@ -109,6 +109,41 @@ int mt_flash_attn_bwd_v3(int dtype, int causal, const void* q, const void* k, co
                          int64_t d, const int64_t* strides, const int* kv_len,
                          void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Grouped-query attention for training and prefill, device pointers ------ */
+/* mt_flash_attn_fwd_varlen / mt_flash_attn_bwd_v3 with H query heads sharing Hkv key / value
+ * heads in groups of G = H / Hkv (Hkv = 1: multi-query); query head h uses kv head h / G.
+ *   q, o, dout, dq:  [B, H, N, d];   k, v, dk, dv:  [B, Hkv, N, d]   (NULL strides: dense)
+ *   m, l:            fp32 [B*H*N], indexed by query head (the forward's may be NULL)
+ * causal and kv_len (device int32 [B], clamped to [0, N], NULL = none) as in those entries: a
+ * padded query attends the valid keys, a row with no key gets O = 0, m = -inf, l = 0, padding
+ * keys get dK = dV = 0 exactly. dK and dV are the sums over the group's query heads, taken
+ * inside the dK/dV pass in head order (no atomics, no read-modify-write): the same bits on
+ * every call. dtype: MT_F32 only, finite inputs (both contractions run on the bf16 MFMA with
+ * three bf16 pieces per fp32 operand, fp32 accuracy). Any N. Requires d <= 128 and 16-B rows:
+ * d, every stride and every base pointer a multiple of 16 bytes.
+ * Forward: one workgroup per (batch, kv head, query block), its waves min(G, 4) query heads of
+ * the group at the same query positions, reading K / V tiles staged once into LDS. Backward:
+ * δ / log2-LSE prep, the dK/dV pass (key on the lane, the group's query heads swept in order
+ * into one register sum), the dQ pass (the forward's packing).
+ * strides (backward): NULL or 8 consecutive triples for q, k, v, o, dout, dq, dk, dv.
+ * Hkv == H is mt_flash_attn_fwd_varlen / mt_flash_attn_bwd_v3: the same launches and bits.
+ * Refused with a status and a mt_last_error() message before any device call: Hkv <= 0,
+ * Hkv > H, H % Hkv != 0, a dtype other than MT_F32, d > 128, rows / strides / bases off 16
+ * bytes, B*H > 65535, a workspace below mt_flash_attn_bwd_gqa_workspace_bytes (which answers
+ * -1 for sizes the entry points refuse). No allocation and no synchronisation: stream-ordered
+ * launches only, capturable into a graph. */
+int mt_flash_attn_fwd_gqa(int dtype, int causal, const void* q, const void* k, const void* v,
+                          void* o, float* m, float* l, int64_t B, int64_t H, int64_t Hkv, int64_t N,
+                          int64_t d, const int64_t* q_strides, const int64_t* k_strides,
+                          const int64_t* v_strides, const int64_t* o_strides, const int* kv_len,
+                          void* stream);
+int64_t mt_flash_attn_bwd_gqa_workspace_bytes(int64_t B, int64_t H, int64_t Hkv, int64_t N, int64_t d);
+int mt_flash_attn_bwd_gqa(int dtype, int causal, const void* q, const void* k, const void* v,
+                          const void* o, const void* dout, const float* m, const float* l,
+                          void* dq, void* dk, void* dv, int64_t B, int64_t H, int64_t Hkv, int64_t N,
+                          int64_t d, const int64_t* strides, const int* kv_len, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
 /* ---- KV-cache decode attention, device pointers ---------------------------- */
 /* Generation: Nq (1..8) new query rows per (batch, head) against a cache of Nk key / value
  * rows, of which the first n = clamp(kv_len[b], 0, Nk) are visible (kv_len: device int32 [B];

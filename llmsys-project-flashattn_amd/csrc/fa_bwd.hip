@@ -85,6 +85,8 @@ static hipError_t launch_prep(const AttnArgs& a, hipStream_t st) {
   else hipLaunchKernelGGL((fa_bwd_prep<T, false>), grid, dim3(256), 0, st, a);
   return hipGetLastError();
 }
+// the fp32 prep alone, for the grouped-query backward (fa_gqa.hip): δ and lse2 are per query row
+hipError_t launch_bwd_prep_f32(const AttnArgs& a, hipStream_t st) { return launch_prep<float>(a, st); }
 
 // ---------------------------------------------------------------------------
 // dK, dV: grid (ceil(N/128), B*H, ceil(d/DT)).

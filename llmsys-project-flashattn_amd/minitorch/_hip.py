@@ -61,6 +61,11 @@ _PROTOS = {
                                         _i64, _i64, _i64, _i64, _i64p, _vp, _vp, _vp]),
     "mt_flash_attn_bwd_v3": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _i64, _i64, _i64, _i64, _i64p, _vp, _vp, _i64, _vp]),
+    "mt_flash_attn_fwd_gqa": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                     _i64p, _i64p, _i64p, _i64p, _vp, _vp]),
+    "mt_flash_attn_bwd_gqa_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64]),
+    "mt_flash_attn_bwd_gqa": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _i64, _i64, _i64, _i64, _i64, _i64p, _vp, _vp, _i64, _vp]),
     "mt_flash_attn_decode_splits": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _i64p, _i64p]),
     "mt_flash_attn_decode_workspace_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64]),
     "mt_flash_attn_decode": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
@@ -395,6 +400,67 @@ def flash_bwd(q, k, v, o, do, m, l, causal: bool = False, dq=None, dk=None, dv=N
     check(lib().mt_flash_attn_bwd_v3(*args, None if kv is None else kv.data_ptr(),
                                      workspace.data_ptr(), workspace.numel() * workspace.element_size(),
                                      st), "mt_flash_attn_bwd_v3")
+    return dq, dk, dv
+
+
+def _gqa_shapes(q, k, v):
+    B, H, N, d = q.shape
+    Hkv = k.shape[1]
+    if k.shape != v.shape or tuple(k.shape) != (B, Hkv, N, d):
+        raise ValueError(f"q [B,H,N,d] / k, v [B,Hkv,N,d] shapes differ: {tuple(q.shape)} {tuple(k.shape)} "
+                         f"{tuple(v.shape)}")
+    return B, H, Hkv, N, d
+
+
+def flash_fwd_gqa(q, k, v, causal: bool = False, out=None, m=None, l=None, stream: Optional[int] = None,
+                  kv_len=None):
+    """Grouped-query forward for training / prefill (mt_flash_attn_fwd_gqa): q [B,H,N,d] fp32,
+    k, v [B,Hkv,N,d] (query head h uses kv head h // (H // Hkv)), any strides with 16-B rows,
+    d <= 128. Returns (O, m, l) laid out as flash_fwd's; kv_len as flash_fwd. Hkv == H is flash_fwd."""
+    torch = _torch()
+    _check_dev(q, k, v)
+    B, H, Hkv, N, d = _gqa_shapes(q, k, v)
+    if not (q.dtype == k.dtype == v.dtype):
+        raise TypeError("q/k/v dtypes differ")
+    out = torch.empty_like(q, memory_format=torch.contiguous_format) if out is None else out
+    m = torch.empty((B, H, N), dtype=torch.float32, device=q.device) if m is None else m
+    l = torch.empty((B, H, N), dtype=torch.float32, device=q.device) if l is None else l
+    st = stream_ptr(q.device) if stream is None else stream
+    kv = _kv_arg(kv_len, B, q.device)
+    check(lib().mt_flash_attn_fwd_gqa(dtype_code(q), int(causal), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                      out.data_ptr(), m.data_ptr(), l.data_ptr(), B, H, Hkv, N, d, strides3(q),
+                                      strides3(k), strides3(v), strides3(out),
+                                      None if kv is None else kv.data_ptr(), st), "mt_flash_attn_fwd_gqa")
+    return out, m, l
+
+
+def flash_bwd_gqa(q, k, v, o, do, m, l, causal: bool = False, dq=None, dk=None, dv=None, workspace=None,
+                  stream: Optional[int] = None, kv_len=None):
+    """Grouped-query backward (mt_flash_attn_bwd_gqa). Returns (dQ [B,H,N,d], dK, dV [B,Hkv,N,d]):
+    dK and dV are summed over each group's query heads inside the kernel."""
+    torch = _torch()
+    _check_dev(q, k, v, o, do, m, l)
+    B, H, Hkv, N, d = _gqa_shapes(q, k, v)
+    dq = torch.empty_like(q, memory_format=torch.contiguous_format) if dq is None else dq
+    dk = torch.empty_like(k, memory_format=torch.contiguous_format) if dk is None else dk
+    dv = torch.empty_like(v, memory_format=torch.contiguous_format) if dv is None else dv
+    if workspace is None:
+        nbytes = lib().mt_flash_attn_bwd_gqa_workspace_bytes(B, H, Hkv, N, d)
+        if nbytes < 0:
+            raise ValueError(lib().mt_last_error().decode(errors="replace"))
+        workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
+    m = m.contiguous().float()
+    l = l.contiguous().float()
+    strides = (ctypes.c_int64 * 24)()
+    for i, t in enumerate((q, k, v, o, do, dq, dk, dv)):
+        strides[3 * i:3 * i + 3] = list(strides3(t))
+    st = stream_ptr(q.device) if stream is None else stream
+    kv = _kv_arg(kv_len, B, q.device)
+    check(lib().mt_flash_attn_bwd_gqa(dtype_code(q), int(causal), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                      o.data_ptr(), do.data_ptr(), m.data_ptr(), l.data_ptr(), dq.data_ptr(),
+                                      dk.data_ptr(), dv.data_ptr(), B, H, Hkv, N, d, strides,
+                                      None if kv is None else kv.data_ptr(), workspace.data_ptr(),
+                                      workspace.numel() * workspace.element_size(), st), "mt_flash_attn_bwd_gqa")
     return dq, dk, dv
 
 

@@ -494,9 +494,11 @@ class HipKernelOps(TensorOps):
         o = torch.empty(B * H * N * d, dtype=torch.float32, device="cuda")
         m = torch.empty(B * H * N, dtype=torch.float32, device="cuda")
         l = torch.empty(B * H * N, dtype=torch.float32, device="cuda")
-        _hip.flash_fwd(_torch_view(Q), _torch_view(K), _torch_view(V), causal,
-                       out=torch.as_strided(o, (B, H, N, d), so), m=m.view(B, H, N), l=l.view(B, H, N),
-                       kv_len=HipKernelOps._kv(kv_len))
+        # K and V with fewer heads than Q: the grouped-query kernels (mt_flash_attn_fwd_gqa)
+        fwd = _hip.flash_fwd if K.shape[1] == H else _hip.flash_fwd_gqa
+        fwd(_torch_view(Q), _torch_view(K), _torch_view(V), causal,
+            out=torch.as_strided(o, (B, H, N, d), so), m=m.view(B, H, N), l=l.view(B, H, N),
+            kv_len=HipKernelOps._kv(kv_len))
         return (_wrap(o, (B, H, N, d), backend, so), _wrap(m, (B, H, N), backend),
                 _wrap(l, (B, H, N), backend))
 
@@ -508,12 +510,19 @@ class HipKernelOps(TensorOps):
         B, H, N, d = Q.shape
         backend = Q.backend
         lay = [_layout_like(t) for t in (Q, K, V)]
-        bufs = [torch.empty(B * H * N * d, dtype=torch.float32, device="cuda") for _ in range(3)]
-        g = [torch.as_strided(b, (B, H, N, d), s) for b, s in zip(bufs, lay)]
-        _hip.flash_bwd(_torch_view(Q), _torch_view(K), _torch_view(V), _torch_view(O),
-                       _torch_view(dO), _torch_view(m), _torch_view(l), causal,
-                       dq=g[0], dk=g[1], dv=g[2], kv_len=HipKernelOps._kv(kv_len))
-        return tuple(_wrap(b, (B, H, N, d), backend, s) for b, s in zip(bufs, lay))
+        # K and V with fewer heads than Q (grouped-query, mt_flash_attn_bwd_gqa): dK and dV at
+        # those heads, laid out like K and V
+        shp = [(B, t.shape[1], N, d) for t in (Q, K, V)]
+        bufs = [torch.empty(B * s[1] * N * d, dtype=torch.float32, device="cuda") for s in shp]
+        g = [torch.as_strided(b, sh, s) for b, sh, s in zip(bufs, shp, lay)]
+        bwd = _hip.flash_bwd if K.shape[1] == H else _hip.flash_bwd_gqa
+        bwd(_torch_view(Q), _torch_view(K), _torch_view(V), _torch_view(O),
+            _torch_view(dO), _torch_view(m), _torch_view(l), causal,
+            dq=g[0], dk=g[1], dv=g[2], kv_len=HipKernelOps._kv(kv_len))
+        return tuple(_wrap(b, sh, backend, s) for b, sh, s in zip(bufs, shp, lay))
+
+    # the flash ops above take K / V with fewer heads than Q up to this head dim (fa_gqa.hip)
+    flash_attention_gqa_max_dim = 128
 
     # reference cuda_kernel_ops.py:605-892; kv_len (optional keyword, [B] valid key counts):
     # key padding through mt_flash_attn_*_varlen

@@ -119,10 +119,16 @@ def _takes_fused_step(module, rows: int, width: int, backend, p_dropout: float) 
 class MultiHeadAttention(Module):
     def __init__(self, n_embd: int, n_head: int, causal: bool = False, p_dropout: float = 0.1,
                  bias: bool = True, backend=None, use_fused_kernel: bool = False,
-                 use_flash_attention: bool = False, n_kv_head=None, rope=None, fused_step: bool = False):
+                 use_flash_attention: bool = False, n_kv_head=None, rope=None, fused_step: bool = False,
+                 fused_gqa: bool = False):
         """n_kv_head: grouped-query attention. The n_head query heads share n_kv_head key / value
         heads in groups of n_head // n_kv_head (query head h uses kv head h // group; 1 is
         multi-query attention). None: n_head, every head its own K and V.
+        fused_gqa: with n_kv_head < n_head, training, the full forward and a prefill's own
+        attention hand the n_kv_head-head K and V to the grouped-query flash kernels
+        (mt_flash_attn_fwd_gqa / _bwd_gqa: dK and dV are summed over the group inside the kernel)
+        instead of repeating them to n_head heads. Needs use_flash_attention=True; a backend
+        without the kernels, or a head dim outside their range, keeps the repeat (per call).
         rope: a RotaryTable (rotary position embedding), or None. Q and K are rotated by their
         tokens' positions right after the projection, so every attention branch and the KV cache
         see rotated tensors: by the rope kernel when use_fused_kernel is set and the backend has
@@ -132,6 +138,9 @@ class MultiHeadAttention(Module):
         TransformerLayer, decides per call); forward itself never changes."""
         super().__init__()
         self.fused_step = bool(fused_step)
+        if fused_gqa and not use_flash_attention:
+            raise ValueError("fused_gqa=True needs use_flash_attention=True")
+        self.fused_gqa = bool(fused_gqa)
         if n_kv_head is None:
             n_kv_head = n_head
         if n_kv_head <= 0 or n_head % n_kv_head:
@@ -174,7 +183,7 @@ class MultiHeadAttention(Module):
     def _repeat_kv(self, x):
         """[B, n_kv_head, a, b] -> [B, n_head, a, b], head h a copy of kv head h // group (the
         order the decode kernel uses): a broadcast multiply by ones, whose backward sums the
-        group's gradients. There is no fused grouped-query training kernel."""
+        group's gradients. (fused_gqa=True skips it on the flash path: self_attention.)"""
         group = self.n_head // self.n_kv_head
         if group == 1:
             return x
@@ -194,9 +203,12 @@ class MultiHeadAttention(Module):
         ``kv_len``: optional per-batch-row count of valid (non-padding) keys: the flash path
         masks keys >= kv_len[b] in the kernel (mt_flash_attn_*_varlen); the other branches add
         the equivalent [B, to_len] padding mask. With n_kv_head < n_head, kT and v hold
-        n_kv_head heads and are repeated to n_head first."""
+        n_kv_head heads and are repeated to n_head first, unless fused_gqa hands them to the
+        grouped-query flash kernels as they are."""
         batch_size, num_head, queries_len, q_dim = q.shape
-        kT, v = self._repeat_kv(kT), self._repeat_kv(v)
+        if not (self.fused_gqa and self.use_flash_attention
+                and q_dim <= getattr(q.backend, "flash_attention_gqa_max_dim", 0) and q_dim % 4 == 0):
+            kT, v = self._repeat_kv(kT), self._repeat_kv(v)
         scale = self.attn_hidden_dim ** 0.5
         if self.use_flash_attention:
             kv = None if kv_len is None else _kv_tensor(kv_len, batch_size, self.backend)
@@ -524,8 +536,9 @@ class TransformerLayer(Module):
                  bias: bool = True, backend=None, use_fused_kernel: bool = False,
                  use_flash_attention: bool = False, causal: bool = True, n_kv_head=None, rope=None,
                  fused_step: bool = False, norm: str = "layer", mlp: str = "gelu", n_experts: int = 8,
-                 moe_top_k: int = 2, moe_routed: bool = False):
-        """norm: "layer" (LayerNorm) or "rms" (FusedRMSNorm with eps = ln_eps); mlp: "gelu" or
+                 moe_top_k: int = 2, moe_routed: bool = False, fused_gqa: bool = False):
+        """fused_gqa: MultiHeadAttention(fused_gqa=...) (needs use_flash_attention=True).
+        norm: "layer" (LayerNorm) or "rms" (FusedRMSNorm with eps = ln_eps); mlp: "gelu" or
         "swiglu" (FeedForward(activation=...)), or "moe": MoEFeedForward with n_experts gated
         experts of which every token takes moe_top_k (moe_routed: MoEFeedForward(routed=...)).
         fused_step (needs use_fused_kernel=True: the layer norms must be FusedLayerNorm): a
@@ -542,7 +555,7 @@ class TransformerLayer(Module):
                                             bias=bias, backend=backend,
                                             use_fused_kernel=use_fused_kernel,
                                             use_flash_attention=use_flash_attention, n_kv_head=n_kv_head,
-                                            rope=rope, fused_step=fused_step)
+                                            rope=rope, fused_step=fused_step, fused_gqa=fused_gqa)
         if mlp not in ("gelu", "swiglu", "moe"):
             raise ValueError(f'mlp must be "gelu", "swiglu" or "moe", got {mlp!r}')
         if mlp == "moe":
@@ -589,8 +602,13 @@ class DecoderLM(Module):
                  use_fused_kernel: bool = False, use_flash_attention: bool = False, n_layer: int = 4,
                  n_kv_head=None, pos_encoding: str = "learned", rope_theta: float = 10000.0,
                  fused_step: bool = False, norm: str = "layer", mlp: str = "gelu", n_experts: int = 8,
-                 moe_top_k: int = 2, moe_routed: bool = False):
-        """norm: "layer", or "rms" for RMSNorm (eps = ln_eps) in every block and before lm_head;
+                 moe_top_k: int = 2, moe_routed: bool = False, fused_gqa: bool = False):
+        """fused_gqa (needs use_flash_attention=True and means something with n_kv_head < n_head):
+        training, the full forward and the prompt's attention of a contiguous, paged or quantised
+        prefill run the grouped-query flash kernels on the n_kv_head-head K and V, forward and
+        backward, instead of repeating them to n_head heads (MultiHeadAttention(fused_gqa=...)).
+        Unset, nothing changes.
+        norm: "layer", or "rms" for RMSNorm (eps = ln_eps) in every block and before lm_head;
         mlp: "gelu", or "swiglu" for the gated MLP silu(x W_gate) * (x W_up), or "moe" for a
         mixture of n_experts such gated MLPs of which a router gives every token moe_top_k
         (MoEFeedForward; a fused_step model runs the cached step's on the routed expert kernels,
@@ -637,7 +655,7 @@ class DecoderLM(Module):
                 n_embd, n_head, p_dropout, ln_eps, bias, backend,
                 use_fused_kernel=use_fused_kernel, use_flash_attention=use_flash_attention,
                 n_kv_head=n_kv_head, rope=self.rope, fused_step=fused_step, norm=norm, mlp=mlp, n_experts=n_experts,
-                moe_top_k=moe_top_k, moe_routed=moe_routed))
+                moe_top_k=moe_top_k, moe_routed=moe_routed, fused_gqa=fused_gqa))
         self.dropout = Dropout(p_dropout)
         self.lm_head = Linear(n_embd, n_vocab, bias, backend)
         self.use_fused_kernel = use_fused_kernel

@@ -128,6 +128,9 @@ class TensorBackend:
         self.flash_attention_bw = ops.flash_attention_bw
         self.flash_attention_causal_fw = ops.flash_attention_causal_fw
         self.flash_attention_causal_bw = ops.flash_attention_causal_bw
+        # the flash ops take K / V with fewer heads than Q when head_dim <= this (grouped-query
+        # training attention; 0: they do not, MultiHeadAttention(fused_gqa=True) keeps the repeat)
+        self.flash_attention_gqa_max_dim = getattr(ops, "flash_attention_gqa_max_dim", 0)
         # generation (optional: a backend without the decode kernels has no KV cache)
         self.flash_attention_decode = getattr(ops, "flash_attention_decode", None)
         self.flash_attention_extend = getattr(ops, "flash_attention_extend", None)

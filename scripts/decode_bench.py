@@ -1553,8 +1553,80 @@ def moe_grouped_legs(args, torch, minitorch, _hip):
         json.dump(res, f, indent=1)
 
 
+def bench_gqa_train(torch, minitorch, B, H, Hkv, N, d, causal, rounds, warmup, inner=16):
+    """Grouped-query attention at a training shape, forward and forward + backward through the
+    tensor interface: the fused path (K / V at Hkv heads into mt_flash_attn_fwd_gqa / _bwd_gqa)
+    against the repeat path (MultiHeadAttention._repeat_kv's broadcast and copies, the fp32 flash
+    kernels at H heads, the broadcast's group sum in the backward), all of it."""
+    backend = minitorch.TensorBackend(minitorch.HipKernelOps)
+    mha = minitorch.MultiHeadAttention(H * d, H, causal=causal, p_dropout=0.0, backend=backend,
+                                       use_flash_attention=True, n_kv_head=Hkv)
+    rng = np.random.default_rng(0)
+    t = lambda shape, grad=True: minitorch.tensor_from_numpy(  # noqa: E731
+        rng.standard_normal(shape).astype(np.float32), backend, requires_grad=grad)
+    # the model's layout: [B, N, heads, d] storage seen as [B, heads, N, d]
+    leaves = [t((B, N, h, d)) for h in (H, Hkv, Hkv)]
+    g = t((B, N, H, d), False).permute(0, 2, 1, 3)
+    attend = (lambda q, k, v: q.flash_attention_causal(k, v)) if causal else (lambda q, k, v: q.flash_attention(k, v))
+
+    def fused():
+        q, k, v = (x.permute(0, 2, 1, 3) for x in leaves)
+        return attend(q, k, v)
+
+    def repeat():
+        q, k, v = (x.permute(0, 2, 1, 3) for x in leaves)
+        return attend(q, mha._repeat_kv(k), mha._repeat_kv(v))
+    paths = {"fused": fused, "repeat": repeat}
+
+    def fwbw(path):
+        def run(i):
+            for x in leaves:
+                x.zero_grad_()
+            path().backward(g)
+        return run
+    legs = {f"{name}_fw": (lambda i, p=p: p()) for name, p in paths.items()}
+    legs.update({f"{name}_fwbw": fwbw(p) for name, p in paths.items()})
+    for fn in legs.values():
+        for i in range(warmup):
+            fn(i)
+    torch.cuda.synchronize()
+    out_f, out_r = paths["fused"]().to_numpy(), paths["repeat"]().to_numpy()
+    names, times = list(legs), {n: [] for n in legs}
+    for r in range(rounds):  # the legs alternate inside every round and swap places between rounds
+        for n in (names if r % 2 == 0 else names[::-1]):
+            times[n].append(_timed(torch, legs[n], inner))
+    med = {n: statistics.median(x) for n, x in times.items()}
+    flops_fw = 4.0 * B * H * N * N * d * (0.5 if causal else 1.0)
+    return {"B": B, "H": H, "Hkv": Hkv, "N": N, "d": d, "causal": causal, "rounds": rounds,
+            "calls_per_timing": inner,
+            **{f"{n}_s_median": med[n] for n in names}, **{f"{n}_s_min": min(times[n]) for n in names},
+            **{f"{n}_s_max": max(times[n]) for n in names},
+            "fw_repeat_over_fused": med["repeat_fw"] / med["fused_fw"],
+            "fwbw_repeat_over_fused": med["repeat_fwbw"] / med["fused_fwbw"],
+            "fused_fw_tflops_whole_path": flops_fw / med["fused_fw"] * 1e-12,
+            "fused_fwbw_tflops_whole_path": 3.5 * flops_fw / med["fused_fwbw"] * 1e-12,
+            "max_abs_fused_minus_repeat": float(np.abs(out_f - out_r).max())}
+
+
+def gqa_train_legs(args, torch, minitorch, _hip):
+    res = {"device": torch.cuda.get_device_name(0), "shapes": []}
+    for hkv in (4, 2, 1):
+        for causal in (False, True):
+            r = bench_gqa_train(torch, minitorch, 8, 16, hkv, 1024, 64, causal, args.rounds, args.warmup)
+            print(json.dumps(r), flush=True)
+            res["shapes"].append(r)
+            torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(args.gqa_train_out), exist_ok=True)
+    with open(args.gqa_train_out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gqa-train-legs", action="store_true",
+                    help="grouped-query training attention, the fused kernels against the repeat path, forward and "
+                         "forward + backward at (8,16,1024,64) with 4, 2 and 1 kv heads, into --gqa-train-out")
+    ap.add_argument("--gqa-train-out", default=os.path.join(ROOT, "profiles", "gqa_train_bench.json"))
     ap.add_argument("--moe-grouped-legs", action="store_true",
                     help="MoEFeedForward routed=True (grouped expert GEMM) against the dense tensor-op path, forward and "
                          "forward + backward, into --moe-grouped-out")
@@ -1613,6 +1685,8 @@ def main():
     from minitorch import _hip
     if args.lib:
         _hip.use_library(os.path.abspath(args.lib), allow_missing=True)
+    if args.gqa_train_legs:
+        return gqa_train_legs(args, torch, minitorch, _hip)
     if args.moe_grouped_legs:
         return moe_grouped_legs(args, torch, minitorch, _hip)
     if args.wq_legs:
